@@ -34,8 +34,16 @@ Output: ONE JSON line on rank 0 (contract in the task statement), with
                rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE, profiles/*_pmc_<kernel>.json).
   tail         the launch's critical problem (longest single problem on one wave), when the job queue
                drained and when the last problem finished (device real-time clock; dg-loop).
-  cpu_baseline the oracle's C restatement (oracle/, test infrastructure) on a bounded sample of the same
-               workload on the host's cores, rank 0, N = 1 only.
+  cpu_baseline (--full only) the oracle's C restatement (oracle/, test infrastructure) on a bounded sample of
+               the same workload on the host's cores, rank 0, N = 1 only; null in a plain run.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: every
+figure of it comes from those launches and from committed counter files.  What takes a run of its own - the CPU
+baseline - is behind --full.
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned on rank 0 as float64 .npy files:
+dg-loop X_save.npy (the step's samples in problem order, before the all-gather), row_cnt.npy (samples per problem,
+-1: None) and problems.npy (the step's problem positions whose rows X_save.npy holds: all of them, or, where the
+samples exceed DUMP_BYTES, a fixed seeded subset sized by the per-problem row bound); first-solve x0.npy, status.npy,
+sqp_iter.npy, qp_iter.npy.  The inputs are Philox draws per problem id, so equal arguments give equal inputs.
 `run(args, engine_factory)` takes another engine (tests/test_distributed.py runs the N = 2 path on gloo with
 the oracle as the engine).
 
@@ -65,6 +73,8 @@ FP64_PEAK_TFLOPS = 78.6  # MI355X FP64 dense peak, vector and matrix (SURVEY.md 
 F_DYN = {3: 6382, 2: 2146, 1: 4 * 14 + 8 * 9 * 4 + 8 * 3 * 4 + 6}
 F_IPM = {3: 3513, 2: 1346, 1: int(2 * 9 * 4 + 2 * 3 * 16 + 64 / 3 + 8 * 16)}
 C_F = {3: 183, 2: 52, 1: 8}
+DUMP_BYTES = 48 << 20    # --dump-outputs: bound on X_save.npy (the other arrays are O(B) values)
+DG_ROWS_MAX = 2 * (100 + 12) + 2   # a problem's rows at most (lib.Solver.data_generation_device's rows_cap rule)
 
 
 def _ur5_counts():
@@ -217,6 +227,25 @@ class GpuEngine:
                 "resident_problems": int(self.solver.get_option("last_groups"))}   # of the last launch
 
 
+def dump_outputs(path, last):
+    """--dump-outputs: the last timed step's arrays (device tensors in `last`) as float64 <path>/<name>.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.cpu().numpy() for k, v in last.items()}
+    if "X_save" in arrays:
+        X, cnt = arrays["X_save"], arrays["row_cnt"]
+        B, n = len(cnt), np.maximum(cnt, 0).astype(np.int64)
+        keep = np.arange(B)
+        if X.nbytes > DUMP_BYTES:   # a fixed subset of the problems, sized before looking at the counts
+            cap = DUMP_BYTES // (DG_ROWS_MAX * X.shape[1] * 8)
+            keep = np.sort(np.random.default_rng(0).permutation(B)[:cap])
+            start = np.cumsum(n) - n
+            idx = np.repeat(start[keep] - (np.cumsum(n[keep]) - n[keep]), n[keep]) + np.arange(int(n[keep].sum()))
+            arrays["X_save"] = X[idx]
+        arrays["problems"] = keep
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def cpu_baseline(nq, workload, B, seconds, threads):
     """Oracle (CPU FP64 restatement, oracle/) on the first problems of the same workload for ~`seconds`:
     first-solve - batches of first solves, one problem per OpenMP thread; dg-loop - the reference's loop at
@@ -270,7 +299,11 @@ def parse(argv=None):
     ap.add_argument("--max-batches", type=int, default=4,
                     help="first-solve: distinct input batches held in HBM (steps cycle through them)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own beside the timed steps: the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float64")
     ap.add_argument("--factor", choices=("mfma", "valu"), default="mfma",
                     help="wave solver's Riccati factorisation: FP64 MFMA (default, nq <= 3) or VALU dot-product steps")
     ap.add_argument("--spec-early", type=int, default=0,
@@ -337,6 +370,7 @@ def run(args, engine_factory=None):
         if world > 1:
             gather_boundary_states(out["x0"])
         if timed:
+            rec["last"] = out
             sqp, qpi = out["sqp_iter"].cpu().numpy(), out["qp_iter"].cpu().numpy()
             rec["solves"] += B
             rec["problems"] += B
@@ -369,6 +403,8 @@ def run(args, engine_factory=None):
         for k in range(count):
             sl = slice(k * B, (k + 1) * B)
             X = order_rows(dict(row_cnt=out["row_cnt"][sl], row_off=out["row_off"][sl], rows_all=out["rows_all"]))
+            if timed and k == count - 1:
+                rec["last"] = dict(X_save=X, row_cnt=out["row_cnt"][sl])
             if world > 1:
                 X = gather_samples(X)
             rec["rows"] += X.shape[0] if timed else 0
@@ -416,9 +452,11 @@ def run(args, engine_factory=None):
         flops = local_flops
     problems = world * args.steps * B
     value = solves / elapsed
+    if rank == 0 and args.dump_outputs and rec.get("last") is not None:
+        dump_outputs(args.dump_outputs, rec["last"])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and engine_factory is None:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and engine_factory is None:
         threads = len(os.sched_getaffinity(0))
         threads = min(threads, int(os.environ.get("OMP_NUM_THREADS", threads)))
         v, n, ns, t = cpu_baseline(nq, args.workload, B, args.cpu_seconds, threads)

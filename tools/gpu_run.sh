@@ -6,7 +6,8 @@
 #   tests_lib=<name>:<files>[:<-k expr>]  GPU test files (comma-separated) on vboc_amd/ab/libvboc_amd_<name>.so
 #                             (VBOC_LIB): the parity suite on a variant build, parity records to <out>/parity_<name>
 #   smoke                     __graft_entry__.smoke()
-#   bench                     the driver's command (bench.py --steps 20 --warmup 5) -> <out>/bench.json
+#   bench                     the driver's command with the CPU baseline (bench.py --steps 20 --warmup 5 --full)
+#                             -> <out>/bench.json
 #   prof                      the same command under rocprofv3 --kernel-trace --stats -> <out>/prof
 #   double                    configs[1]: the double pendulum's 10k dg-loop and first-solve lines
 #   doubleab                  the same per build (product and every vboc_amd/ab/*.so), same box, no CPU baseline
@@ -40,13 +41,13 @@ for step in "$@"; do
                    python -u -m pytest $(echo $files | tr , ' ') -m gpu -x -v --timeout 300 --timeout-method thread \
                    ${k:+-k "$k"} > $O/pytest_lib_$n.log 2>&1;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1;;
-    bench) run bench 420 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; cat $O/bench.json;;
+    bench) run bench 420 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; cat $O/bench.json;;
     prof) (cd /tmp && export TMPDIR=/tmp && run prof 420 rocprofv3 --kernel-trace --stats --output-format csv \
              -d $O/prof -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu --progress 30 \
              > $O/bench_prof.json 2> $O/bench_prof.err) || exit $?;;
-    double) run double_dg 200 python bench.py --nq 2 --batch 10000 --steps 1 --warmup 1 > $O/bench_double_dg.json \
+    double) run double_dg 200 python bench.py --nq 2 --batch 10000 --steps 1 --warmup 1 --full > $O/bench_double_dg.json \
               2> $O/bench_double_dg.err &&
-            run double_fs 200 python bench.py --workload first-solve --nq 2 --batch 10000 --steps 1 --warmup 1 \
+            run double_fs 200 python bench.py --workload first-solve --nq 2 --batch 10000 --steps 1 --warmup 1 --full \
               > $O/bench_double_fs.json 2> $O/bench_double_fs.err;;
     doubleab) for L in $R/vboc_amd/libvboc_amd.so $R/vboc_amd/ab/*.so; do   # configs[1] lines per build, same box
                 [ -f "$L" ] || continue
