@@ -81,8 +81,10 @@ struct WaveLayout {
   // OC: per-pass constant of the vector / forward recursion; OACL: closed-loop A + B K (row-major)
   // ring windows [lo, lo + W): factor [0, OC) (writes back [OK, OC)), or with FAC1 its inputs [0, W_FIN); vector pass
   // [OPE, OX); forward sweep [OC, OX); costate [0, W_COS): A (and B) to the end of lambda_u
-  static constexpr int W_FAC = OC, W_FIN = even_up(ODA), LO_VEC = OPE, W_VEC = OX - OPE, LO_FWD = OC, W_FWD = OX - OC,
-                       W_COS = even_up(OQU + NZ);
+  // W_FINV: the inputs and DA, the predictor gradient (VFUSE, the triple: the factorisation also runs the predictor's
+  // vector step; 78 doubles, still one LDS-DMA)
+  static constexpr int W_FAC = OC, W_FIN = even_up(ODA), W_FINV = even_up(ODA + NZ), LO_VEC = OPE, W_VEC = OX - OPE,
+                       LO_FWD = OC, W_FWD = OX - OC, W_COS = even_up(OQU + NZ);
   // LDS-DMA rings (global_load_lds_dwordx4: one wave-instruction lands 64 lanes x 16 B = 128 doubles):
   // the factorisation streams its window two stages ahead through 4 slots of 2 KiB (two DMAs per
   // stage), the vector / forward / costate recursions six stages ahead through 8 slots of 1 KiB
@@ -317,8 +319,13 @@ __device__ unsigned long long g_wave_prof[16];
 //            pre-pass re-read the gradient with K, A_cl, P e);
 //   8 KFM    the forward sweep's constant pass stores k_f - M nu over k_f, and the step-length pass reads it instead
 //            of re-reading M and chol(Ru) to recompute it.
+//  16 VFUSE  (round 7; the triple only: needs FAC1, A_cl formed inside the factorisation and Ru^-1 in closed form)
+//            the predictor's vector step p_k = c'_k + A_cl' p_{k+1}, k_f = -Ru^-1 (g_u + B'(P e + p_{k+1})) runs inside
+//            factor_mfma one stage behind the matrix recursion, on the ring slot that holds all its operands; k_f
+//            goes to the record with the stage's write-back.  vec<ODA> keeps only the lin = sum Y'k_f pass and
+//            stage 0.  Per row the operations and their order are those of vec (bit-identical).
 #ifndef VBOC_FUSE
-#define VBOC_FUSE 15
+#define VBOC_FUSE 31
 #endif
 
 // HC: the Cartesian path-constraint rows (vboc_set_path_constraint; oracle/vboc_oracle.c hc_*, Lane::hc_*) on
@@ -1164,6 +1171,9 @@ struct Coop {
 #define VBOC_RINV 1
 #endif
   static constexpr bool RINV = VBOC_RINV && FM && NU == 3;
+  // VFUSE (bit 16 of VBOC_FUSE): the predictor's vector step inside factor_mfma, see vstep there
+  static constexpr bool VFUSE = FAC1 && ACL_FUSED && RINV && (VBOC_FUSE & 16);
+  static_assert(!VFUSE || (L::W_FINV <= OK && L::W_FINV <= 128), "VFUSE: A .. DA in one LDS-DMA, in front of the outputs");
   static_assert(((NX + NU - 1) >> 2) <= HR0 + 1, "H_u spans two accumulator registers");
   __device__ __forceinline__ static constexpr int hrow(int row) { return (row & 3) + 4 * ((row >> 2) - HR0); }
   // The loop body is written for a low VALU count (the wave solver is VALU-issue bound): loop-invariant
@@ -1212,8 +1222,10 @@ struct Coop {
     }
     // FAC1: the window is the stage's inputs [A, K) (A, B, z .. lambda_u, e, D, DA): the outputs [K, A_cl] are
     // written into the slot by this sweep before the write-back; k_f and C keep stale slot words, which the record
-    // holds only until the vector passes rewrite them (neither is read before)
-    constexpr int WF = FAC1 ? L::W_FIN : L::W_FAC, P = (WF + 127) / 128;
+    // holds only until the vector passes rewrite them (neither is read before).  VFUSE: the window also carries DA
+    // (the predictor gradient) and the slot's k_f words get the stage's k_f (vstep) before the write-back; C stays
+    // stale (the forward sweep's constant pass and prep_corr rewrite it before anything reads it)
+    constexpr int WF = VFUSE ? L::W_FINV : (FAC1 ? L::W_FIN : L::W_FAC), P = (WF + 127) / 128;
     static_assert(!FAC1 || P == 1, "the factorisation's inputs fit one LDS-DMA");
     auto fdma = [&](int j) {
       const int kk = N - 1 - j >= 0 ? N - 1 - j : 0;
@@ -1264,8 +1276,57 @@ struct Coop {
     fdma(0);
     fdma(1);
     bool ok = true;
+    // VFUSE: the predictor's vector step of the stage held in slot sl, run once acl_slot has completed the slot
+    // (A_cl, K, Ru^-1, P e of this sweep; B and DA = [g_x, g_u] of the window): vec's three sub-passes on one stage,
+    //   c' = g_x + K'g_u + A_cl' P e,  p = c' + A_cl' p_next,  v = P e + p_next,  k_f = -Ru^-1 (g_u + B'v),
+    // each row with vec's operations in vec's order (same bits).  Lane i owns row i of c' and p (lanes past NX repeat
+    // row NX - 1), lane a row a of g_u + B'v and of k_f (lanes past NU repeat row NU - 1 and write the junk tail);
+    // p_next and g_u + B'v reach the lanes by v_readlane.  It reads only words that this sweep wrote or the DMA
+    // landed for this stage, so the ZERO-word rule above has nothing to add.  LDS and VALU work only: no VMEM op,
+    // the counted waits stay exact.  pcur: p of the stage above (p_N = g_N first), carried in registers.
+    // The step's operand reads issue at the top of the trip, but its k_f (kfv) goes into the slot and the slot to
+    // the record only at the END of the trip, with the stage's own output stores: the step's ~22 dependent FP64
+    // operations then have the whole MFMA chain to overlap with.  With the write-back at the top, right behind the
+    // step, the chain ran alone in front of the ring wait and the launch was 4 % SLOWER than the separate vector
+    // pass; at the end it is 4-5 % faster (profiles/r07_probe_vfuse_ab.jsonl).
+    double pcur = 0.0, kfv = 0.0;
+    const int kfo = t < NU ? OKF + t : FJUNK;
+    if constexpr (VFUSE) pcur = st(N, ODA + (t < NX ? t : NX - 1));
+    auto vstep = [&](int sl) {
+      const int kb = fslot(sl);
+      const int i = t < NX ? t : NX - 1, a = t < NU ? t : NU - 1;
+      double gu[NU], kk[NU], lr[NU], ac[NX], pe[NX], bb[NX];
+      const double gx = s[kb + ODA + i], gua = s[kb + ODA + NX + a];
+      UNR for (int q = 0; q < NU; ++q) {
+        gu[q] = s[kb + ODA + NX + q];
+        kk[q] = s[kb + OK + q * NX + i];
+        lr[q] = s[kb + OLR + a * NU + q];
+      }
+      UNR for (int q = 0; q < NX; ++q) {
+        ac[q] = s[kb + OACL + q * NX + i];
+        pe[q] = s[kb + OPE + q];
+        bb[q] = s[kb + OB + q * NU + a];
+      }
+      double pv[NX];
+      UNR for (int q = 0; q < NX; ++q) pv[q] = rdlane(pcur, q);
+      double c = gx;
+      UNR for (int q = 0; q < NU; ++q) c += kk[q] * gu[q];
+      UNR for (int q = 0; q < NX; ++q) c += ac[q] * pe[q];
+      double p0 = c, p1 = 0.0;
+      UNR for (int q = 0; q < NX; q += 2) p0 += ac[q] * pv[q];
+      UNR for (int q = 1; q < NX; q += 2) p1 += ac[q] * pv[q];
+      double x = gua;
+      UNR for (int q = 0; q < NX; ++q) x += bb[q] * (pe[q] + pv[q]);
+      double kf = 0.0;
+      UNR for (int b = 0; b < NU; ++b) kf += lr[b] * rdlane(x, b);
+      kfv = -kf;
+      pcur = p0 + p1;
+    };
     auto wb_prev = [&](int j, int k) {
-      if constexpr (ACL_FUSED) {
+      if constexpr (VFUSE) {
+        acl_slot((j - 1) % L::NSF);
+        vstep((j - 1) % L::NSF);   // the write-back follows at the end of the trip
+      } else if constexpr (ACL_FUSED) {
         acl_slot((j - 1) % L::NSF);                   // LDS ops of this wave run in order: the write-back's
         ring_wb<OK, L::OX>((j - 1) % L::NSF, k + 1);  // reads of the slot see them
       } else {
@@ -1372,6 +1433,14 @@ struct Coop {
       s[kb + yofs] = yv;
       s[kb + pofs] = pg[0];
       s[kb + pofs + 4] = pg[1];
+      if constexpr (VFUSE) {
+        // stage k + 1: its k_f into its slot, then the slot's outputs to the record (the slot is refilled by the
+        // DMA of the next trip at the earliest)
+        if (j >= 1) {
+          s[fslot((j - 1) % L::NSF) + kfo] = kfv;
+          ring_wb<OK, L::OX>((j - 1) % L::NSF, k + 1);
+        }
+      }
       lsync();
       FS4(3)
       FS5(3)
@@ -1388,12 +1457,20 @@ struct Coop {
     {
       const int j = N - 1, kb = fslot(j % L::NSF);
       if (j >= 1) {
-        if constexpr (ACL_FUSED) {
+        if constexpr (VFUSE) {
+          acl_slot((j - 1) % L::NSF);
+          vstep((j - 1) % L::NSF);
+          s[fslot((j - 1) % L::NSF) + kfo] = kfv;
+          ring_wb<OK, L::OX>((j - 1) % L::NSF, 1);
+        } else if constexpr (ACL_FUSED) {
           acl_slot((j - 1) % L::NSF);
           ring_wb<OK, L::OX>((j - 1) % L::NSF, 1);
         } else {
           ring_wb<OK, OC>((j - 1) % L::NSF, 1);
         }
+      }
+      if constexpr (VFUSE) {
+        if (t < NX) s[L::PV + t] = pcur;   // p_1 for vec's stage-0 block (N == 1: p_N)
       }
       // stage 0's window was issued two sweeps ago (and the clamped repeats after it): retire all
       vmwait<0>();
@@ -1470,13 +1547,16 @@ struct Coop {
     }
   }
   // PRE == false: the constants c' are already in OC (CCORR: prep_corr formed them)
-  template <int OG, bool PRE = true>
+  // SWEPT (VFUSE, the predictor): factor_mfma has run the recursion - k_f of stages 1..N-1 is in the records and
+  // p_1 in PV; what remains is lin = sum Y'k_f (each lane its stages in the same order, then the same wsum) and
+  // stage 0
+  template <int OG, bool PRE = true, bool SWEPT = false>
   __device__ __forceinline__ bool vec(double (&w0)[M0], double (&nun)[NQ]) {
     fresh();
     // p_k = c'_k + A_cl,k' p_{k+1},  c'_k = g_x + K'g_u + A_cl' PE_k  (lane i: row i of p);
     // v_k = PE_k + p_{k+1} is kept for k_f.  c' is formed stage-parallel first (-> OC).
     SPROF_DECL(2)
-    if constexpr (PRE) {
+    if constexpr (PRE && !SWEPT) {
       constexpr int NKK = (NU * NX) / 2;
       for (int k = 1 + t; k < N; k += 64) {
         Cov<OG, NZ> gg;   // the gradient slot only
@@ -1505,6 +1585,7 @@ struct Coop {
       __syncthreads();
     }
     SPROF(0)
+    if constexpr (!SWEPT) {
     double pcur = st(N, OG + (t < NX ? t : NX - 1));
     if (t < NX) s[L::PV + t] = pcur;
     const int cnt = N - 1;   // stages N-1 .. 1
@@ -1596,11 +1677,24 @@ struct Coop {
     }
     if (t < NX) s[L::PV + t] = pcur;
     __syncthreads();
+    }
     SPROF(1)
     // k_f = -Ru^-1 (g_u + B'v) per stage, lin = sum Y'k_f  (stage-parallel)
     double lin[NQ];
     UNR for (int j = 0; j < NQ; ++j) lin[j] = 0.0;
     constexpr int NBB = (NX * NU + 1) / 2, NLY = (OPE - (OLR & ~1) + 1) / 2;   // B; chol(Ru) (.. M, with the old order), Y
+    if constexpr (SWEPT) {
+      // k_f (factor_mfma's vstep, through the write-back) and Y from the records
+      constexpr int F0_ = OKF & ~1, NF = (OKF + NU - F0_ + 1) / 2, Y0_ = OY & ~1, NY = (OPE - Y0_ + 1) / 2;
+      for (int k = 1 + t; k < N; k += 64) {
+        double kf[2 * NF], yy[2 * NY];
+        ldr<F0_, NF>(k, kf);
+        ldr<Y0_, NY>(k, yy);
+        __builtin_amdgcn_sched_barrier(0);
+        UNR for (int j = 0; j < NQ; ++j)
+          UNR for (int a = 0; a < NU; ++a) lin[j] += yy[(OY - Y0_) + a * NQ + j] * kf[(OKF - F0_) + a];
+      }
+    } else
     for (int k = 1 + t; k < N; k += 64) {
       double bb[2 * NBB], ly[2 * NLY];
       Cov<OG + NX, NU> gg;   // g_u of the gradient slot
@@ -2196,7 +2290,7 @@ struct Coop {
         if constexpr (!ACL_FUSED) VREP(3, acl_pass());
         CPROF(3)
         bool okv;
-        VREP(4, okv = vec<ODA>(w0, nun));
+        VREP(4, (okv = vec<ODA, true, VFUSE>(w0, nun)));   // VFUSE: factor_mfma ran the sweep (phase 3)
         CPROF(4)
         if (!(okf && okv)) { qst = -1; break; }
         double aa, c0, c1, c2;
@@ -2322,6 +2416,13 @@ void k_wave(Work w, Opts o, Inputs in, SlotState ss, WaveJobs jb) {
       atomicAdd(ss.done, 1u);
     }
   }
+  // Code-object layout.  The arm's k_ls<4> lies behind this kernel and calls Lane<4>::merit, which lies in front of
+  // it, through a PC-relative literal; tests/test_isa_guard.py pins that literal with the arm's other instructions.
+  // VFUSE made k_wave<3, true> 288 bytes shorter, one 256-byte function-alignment step, which would move the literal.
+  // 96 s_nop (384 bytes), run once by a workgroup that has found the job queue empty, put the kernel's end back
+  // into the same alignment step, so every arm kernel keeps the bytes the GPU suite validated.  To be dropped when
+  // the arm's digests are next re-recorded after a GPU run of tests/test_ur5.py.
+  if constexpr (NQ == 3 && FM && !HC && Coop<NQ, FM, HC>::VFUSE) asm volatile(".rept 96\n\ts_nop 0\n\t.endr");
 }
 
 // compact the slots still iterating (phase 1 at a round boundary) into list[]
