@@ -64,6 +64,32 @@ int vboc_fit_train(vboc_fit_handle h, const vboc_fit_run_t* run, void* stream);
  * idx_out (device int32 [steps][minibatch]). */
 int vboc_fit_sample(vboc_fit_handle h, long long n, long long n_new, int steps, int* idx_out, void* stream);
 
+/* Pruning (VBOC/vboc.py:564-625: prune.global_unstructured with L1Unstructured over the six tensors, a refit under
+ * the masks with the same optimizer, prune.remove).  The six arguments are device float32 0 / 1 masks in the
+ * parameters' layouts; all six NULL removes the mask (the zeros stay, every parameter trains again).  Setting a
+ * mask zeroes the masked parameters; while it is active, set_params stores parameter * mask, and a fit's Adam step
+ * masks the gradient and holds the masked parameters at zero - the effective network of torch's reparametrised
+ * loop, bit for bit. */
+int vboc_fit_set_mask(vboc_fit_handle h, const float* W0, const float* b0, const float* W1, const float* b1,
+                      const float* W2, const float* b2, void* stream);
+/* The active mask, all ones when there is none (test hook, and the way the mask reaches Python). */
+int vboc_fit_get_mask(vboc_fit_handle h, float* W0, float* b0, float* W1, float* b1, float* W2, float* b2,
+                      void* stream);
+/* Selects, on the device, the nprune parameters of smallest magnitude among the current ones (padding excluded),
+ * makes them the mask and zeroes them.  Exactly nprune entries are pruned (*pruned, host); ties at the threshold
+ * magnitude are pruned in the order W0, b0, b1, W2, b2, W1, row-major within each tensor (torch leaves its own tie
+ * choice unspecified).  The caller computes nprune = round(amount * count) as torch does.  VBOC_FIT_EARG while a
+ * mask is active. */
+int vboc_fit_prune(vboc_fit_handle h, long long nprune, long long* pruned, void* stream);
+
+/* Forward-only evaluation of the current parameters over n contiguous device rows F [n][ld] (the inputs; then the
+ * float32 target, used when y is NULL): out (device float32 [n], optional) receives the model outputs, y (device
+ * float64 [n], optional) gives the targets, stats (host double[3]) = sum of (out - y)^2 in float64, the safety
+ * margin max (out - y) / y over the rows with out > y (:638-642; 0 when there is no such row), the count of those
+ * rows.  Fixed-order reductions: two calls return the same bits.  n = 0 returns zeros. */
+int vboc_fit_eval(vboc_fit_handle h, const float* F, long long n, int ld, const double* y, float* out,
+                  double* stats, void* stream);
+
 int vboc_fit_info(vboc_fit_handle h, int* hidden_padded, int* splits, long long* adam_steps,
                   unsigned long long* draws);
 const char* vboc_fit_last_error(void);

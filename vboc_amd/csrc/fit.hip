@@ -17,6 +17,9 @@
 //   k_adam      the partial sums reduced in a fixed order, torch.optim.Adam's update (single-tensor path),
 //               W1 rewritten as the packed MFMA fragments of the next step's two products
 //
+// Beside the step (VBOC/vboc.py:564-642): k_prune selects the global L1 pruning mask, k_adam holds masked entries at
+// zero during the refit under it, k_eval is the forward-only pass behind the RMSE and the safety margin.
+//
 // Every operand streamed from L2 / MALL (W1 twice, H1 and dH2 for dW1) is stored fragment-packed (pk()): a wave's
 // B (or A) fragment of one 16 x 16 block is 1 KB contiguous, so each load instruction moves whole 256-B lines.
 //
@@ -52,6 +55,7 @@ struct Args {
   float* P;                   // parameters: [W0 (HP x NIN) | b0 | b1 | w2 (HP each) | b2 (4) | W1 (HP x HP)]
   float* M;                   // Adam exp_avg, same layout
   float* V;                   // Adam exp_avg_sq
+  const float* K;             // 0 / 1 pruning mask, same layout (padding 0); null when no mask is active
   float* Wf;                  // W1 packed as the forward product's B fragments: pk(j, k, HP / 16)
   float* Wb;                  // W1 packed as the backward product's B fragments: element W1[j][c] at pk(c, j, HP / 16)
   int* idx;                   // this step's minibatch row indices [Bt]
@@ -617,8 +621,16 @@ __global__ __launch_bounds__(256) void k_adam(Args a) {
       const size_t o = (size_t)(tj * 32 + rj) * HP + tc * 32 + rc;
       float g = a.dW1p[o];
       for (int s = 1; s < a.S; ++s) g += a.dW1p[(size_t)s * HP * HP + o];
+      // under a mask (prune.global_unstructured's reparametrisation, restated as zero-and-hold): the gradient
+      // reaching a pruned entry is zero and the entry stays zero
+      float mk = 1.f;
+      if (a.K) {
+        mk = a.K[Ly::W1 + o];
+        g *= mk;
+      }
       float p = a.P[Ly::W1 + o], m = a.M[Ly::W1 + o], v = a.V[Ly::W1 + o];
       adam(p, m, v, g, k);
+      if (mk == 0.f) p = 0.f;
       a.P[Ly::W1 + o] = p;
       a.M[Ly::W1 + o] = m;
       a.V[Ly::W1 + o] = v;
@@ -649,8 +661,14 @@ __global__ __launch_bounds__(256) void k_adam(Args a) {
   if (q == 0 && e < Ly::SMALL) {
     float s = red[0][tid];
     for (int i = 1; i < 16; ++i) s += red[i][tid];
+    float mk = 1.f;
+    if (a.K) {
+      mk = a.K[e];
+      s *= mk;
+    }
     float p = a.P[e], m = a.M[e], v = a.V[e];
     adam(p, m, v, s, k);
+    if (mk == 0.f) p = 0.f;
     a.P[e] = p;
     a.M[e] = m;
     a.V[e] = v;
@@ -670,8 +688,10 @@ __global__ void k_pack(float* P, float* Wf, float* Wb, float* W0, float* b0, flo
     } else {
       const float v = (j < H && c < H) ? W1[j * H + c] : 0.f;
       P[Ly::W1 + i] = v;
-      Wf[pk(j, c, HP / 16)] = v;
-      Wb[pk(c, j, HP / 16)] = v;
+      if (Wf) {
+        Wf[pk(j, c, HP / 16)] = v;
+        Wb[pk(c, j, HP / 16)] = v;
+      }
     }
   }
   if (i < HP) {
@@ -694,6 +714,257 @@ __global__ void k_pack(float* P, float* Wf, float* Wb, float* W0, float* b0, flo
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// pruning (VBOC/vboc.py:564-625) and the forward-only evaluation (:555-559, :631-642)
+// ------------------------------------------------------------------------------------------------
+// The padded parameter layout with run-time sizes (Lay<NIN, HP> for the kernels that are no hot path).
+struct LayR {
+  int nin, hp, H, b0, b2, w1, total;
+};
+
+// a real (unpadded) entry of the layout
+__device__ __forceinline__ bool lay_real(const LayR& L, int i) {
+  if (i < L.b0) return i / L.nin < L.H;
+  if (i < L.b2) return (i - L.b0) % L.hp < L.H;     // b0, b1, w2
+  if (i < L.w1) return i == L.b2;
+  const int o = i - L.w1;
+  return o / L.hp < L.H && o % L.hp < L.H;
+}
+
+// the mask of an unpruned model: 1 on the real entries, 0 on the padding
+__global__ void k_mask_ones(float* K, LayR L) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < L.total) K[i] = lay_real(L, i) ? 1.f : 0.f;
+}
+
+// P = mask ? P : 0, and W1's packed fragments rewritten from it
+__global__ void k_mask_apply(float* P, const float* K, float* Wf, float* Wb, LayR L) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= L.total) return;
+  float v = P[i];
+  if (K[i] == 0.f) {
+    v = 0.f;
+    P[i] = 0.f;
+  }
+  if (i >= L.w1) {
+    const int o = i - L.w1, j = o / L.hp, c = o % L.hp;
+    Wf[pk(j, c, L.hp / 16)] = v;
+    Wb[pk(c, j, L.hp / 16)] = v;
+  }
+}
+
+constexpr int PNT = 1024;           // k_prune's one workgroup
+
+// L1Unstructured over all six tensors: the mask that drops the `nprune` real entries of smallest |p|.
+// One workgroup.  The bit pattern of |p| is monotone in |p|, so the nprune-th smallest magnitude T is found by a
+// radix select, most significant byte first: each pass histograms one byte of the keys that share the prefix found
+// so far (per-wave LDS histograms, summed in wave order) and descends into the bin that holds the nprune-th key.
+// Entries below T are pruned; of the entries equal to T the first `need` in buffer order (W0, b0, b1, W2, b2, W1,
+// each row-major) are: every thread owns a contiguous index range, so an exclusive scan of the per-thread tie
+// counts ranks the ties.  Integer counts only: the same parameters always give the same mask.
+__global__ __launch_bounds__(PNT) void k_prune(const float* P, float* K, LayR L, long long nprune,
+                                                long long* pruned) {
+  __shared__ unsigned hist[PNT / 64][256];
+  __shared__ unsigned tot[256];
+  __shared__ unsigned cnt[PNT];
+  __shared__ unsigned s_prefix, s_need, s_pruned;
+  const int tid = threadIdx.x, wv = tid >> 6;
+  unsigned prefix = 0u, need = (unsigned)nprune;      // the need-th smallest (from 1) of the keys under `prefix`
+  if (tid == 0) s_pruned = 0u;
+  for (int pass = 0; pass < 4 && nprune > 0; ++pass) {
+    const int shift = 24 - 8 * pass;
+    for (int i = tid; i < (PNT / 64) * 256; i += PNT) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < L.total; i += PNT) {
+      if (!lay_real(L, i)) continue;
+      const unsigned key = __float_as_uint(P[i]) & 0x7FFFFFFFu;
+      if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[wv][(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 256) {
+      unsigned s = 0u;
+      for (int w = 0; w < PNT / 64; ++w) s += hist[w][tid];
+      tot[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      unsigned cum = 0u;
+      int b = 0;
+      for (; b < 255; ++b) {
+        if (cum + tot[b] >= need) break;
+        cum += tot[b];
+      }
+      s_prefix = (prefix << 8) | (unsigned)b;
+      s_need = need - cum;
+    }
+    __syncthreads();
+    prefix = s_prefix;
+    need = s_need;
+    __syncthreads();
+  }
+  // prefix = the threshold key T, need = how many of the entries equal to T are pruned
+  const int C = (L.total + PNT - 1) / PNT;
+  const int lo = tid * C, hi = min(lo + C, L.total);
+  unsigned c = 0u;
+  if (nprune > 0)
+    for (int i = lo; i < hi; ++i)
+      if (lay_real(L, i) && (__float_as_uint(P[i]) & 0x7FFFFFFFu) == prefix) ++c;
+  cnt[tid] = c;
+  __syncthreads();
+  for (int d = 1; d < PNT; d <<= 1) {
+    const unsigned add = tid >= d ? cnt[tid - d] : 0u;
+    __syncthreads();
+    cnt[tid] += add;
+    __syncthreads();
+  }
+  unsigned rank = cnt[tid] - c, np = 0u;
+  for (int i = lo; i < hi; ++i) {
+    float keep = 0.f;
+    if (lay_real(L, i)) {
+      const unsigned key = __float_as_uint(P[i]) & 0x7FFFFFFFu;
+      const bool drop = nprune > 0 && (key < prefix || (key == prefix && rank++ < need));
+      keep = drop ? 0.f : 1.f;
+      np += drop;
+    }
+    K[i] = keep;
+  }
+  atomicAdd(&s_pruned, np);
+  __syncthreads();
+  if (tid == 0) *pruned = (long long)s_pruned;
+}
+
+constexpr int EVG = 2048;           // most workgroups (= partial records) of one evaluation
+
+struct EvalArgs {
+  const float* P;
+  const float* Wf;
+  const float* F;             // rows [n][ld]: NIN inputs (then the float32 target, read when y is null)
+  const double* y;            // float64 targets [n], or null
+  float* out;                 // model outputs [n], or null
+  double* part;               // per-workgroup records [gridDim.x][3]: sum of squared errors, margin, rows above
+  long long n;
+  int ld, nblk;
+};
+
+// Forward only, the training forward's arithmetic (k_fwd_bwd: the W0 layer, gemm_rows on Wf, the output layer), 16
+// contiguous rows per workgroup and round; the last block's rows are loaded with clamped indices and masked on
+// output.  Thread r < 16 keeps row r's running sums over the workgroup's blocks (in block order), thread 0 adds the
+// 16 in lane order: a fixed order throughout, no floating-point atomics.
+template <int NIN, int HP>
+__global__ __launch_bounds__(256) void k_eval(EvalArgs e) {
+  using Ly = Lay<NIN, HP>;
+  constexpr int NT = HP / 64;
+  constexpr int LD = HP + 4;
+  __shared__ __attribute__((aligned(16))) float H1[R2 * LD];
+  __shared__ float xs[R2 * NIN], red[4][R2];
+  __shared__ double ys[R2], rs[R2], rm[R2], rc[R2];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const float* P = e.P;
+  double sse = 0.0, mg = -INFINITY, cn = 0.0;
+  for (int blk = blockIdx.x; blk < e.nblk; blk += gridDim.x) {
+    const long long row0 = (long long)blk * R2;
+    if (tid < R2 * NIN) {
+      const long long row = min(row0 + tid / NIN, e.n - 1);
+      xs[tid] = e.F[(size_t)row * e.ld + tid % NIN];
+    } else if (tid >= 192 && tid < 192 + R2) {
+      const long long row = min(row0 + (tid - 192), e.n - 1);
+      ys[tid - 192] = e.y ? e.y[row] : (double)e.F[(size_t)row * e.ld + NIN];
+    }
+    __syncthreads();
+    for (int c = tid; c < HP; c += 256) {
+      float wc[NIN];
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) wc[i] = P[Ly::W0 + c * NIN + i];
+      const float bc = P[Ly::B0 + c];
+#pragma unroll
+      for (int r = 0; r < R2; ++r) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) s = fmaf(xs[r * NIN + i], wc[i], s);
+        H1[r * LD + c] = fmaxf(s + bc, 0.f);
+      }
+    }
+    __syncthreads();
+    f4 acc[NT];
+#pragma unroll
+    for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
+    gemm_rows<HP, NT, LD>(H1, e.Wf, w, lane, lr, lq, acc);
+    float op[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int j = 16 * (w + 4 * u) + lr;
+      const float bj = P[Ly::B1 + j], wj = P[Ly::W2 + j];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) op[g] = fmaf(fmaxf(acc[u][g] + bj, 0.f), wj, op[g]);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) op[g] += __shfl_xor(op[g], o);
+    }
+    if (lr == 0) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) red[w][4 * lq + g] = op[g];
+    }
+    __syncthreads();
+    if (tid < R2 && row0 + tid < e.n) {
+      const float s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+      const float o = fmaxf(s + P[Ly::B2], 0.f);
+      if (e.out) e.out[row0 + tid] = o;
+      const double d = (double)o - ys[tid];
+      sse += d * d;
+      if (d > 0.0) {
+        mg = fmax(mg, d / ys[tid]);
+        cn += 1.0;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < R2) {
+    rs[tid] = sse;
+    rm[tid] = mg;
+    rc[tid] = cn;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int r = 1; r < R2; ++r) {
+      sse += rs[r];
+      mg = fmax(mg, rm[r]);
+      cn += rc[r];
+    }
+    double* rec = e.part + 3 * (size_t)blockIdx.x;
+    rec[0] = sse;
+    rec[1] = mg;
+    rec[2] = cn;
+  }
+}
+
+// the workgroup records of k_eval in a fixed order; the margin of "no row above its target" is 0
+__global__ __launch_bounds__(256) void k_eval_final(const double* part, int G, double* stats) {
+  __shared__ double rs[256], rm[256], rc[256];
+  const int tid = threadIdx.x;
+  double sse = 0.0, mg = -INFINITY, cn = 0.0;
+  for (int q = tid; q < G; q += 256) {
+    sse += part[3 * q];
+    mg = fmax(mg, part[3 * q + 1]);
+    cn += part[3 * q + 2];
+  }
+  rs[tid] = sse;
+  rm[tid] = mg;
+  rc[tid] = cn;
+  __syncthreads();
+  if (tid == 0) {
+    for (int r = 1; r < 256; ++r) {
+      sse += rs[r];
+      mg = fmax(mg, rm[r]);
+      cn += rc[r];
+    }
+    stats[0] = sse;
+    stats[1] = cn > 0.0 ? mg : 0.0;
+    stats[2] = cn;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -704,6 +975,10 @@ struct vboc_fit {
   int total, rec;
   float *P = nullptr, *M = nullptr, *V = nullptr, *Wf = nullptr, *Wb = nullptr;
   float *H1p = nullptr, *dH2p = nullptr, *part = nullptr, *dW1p = nullptr;
+  float* K = nullptr;                 // the pruning mask (padded layout); all real entries 1 while none is active
+  bool masked = false;
+  double* epart = nullptr;            // k_eval's records [EVG][3], then the three totals
+  long long* npruned = nullptr;       // k_prune's count
   int* idx[2] = {nullptr, nullptr};
   State* st = nullptr;
   State* st_host = nullptr;           // pinned
@@ -771,12 +1046,36 @@ template <int NIN, int HP>
 static int rec_of() { return Lay<NIN, HP>::REC; }
 
 static void pack(vboc_fit* h, float* W0, float* b0, float* W1, float* b1, float* W2, float* b2, int unpack,
-                 float* src) {
+                 float* src, bool frags = true) {
   const int nthr = h->hp * h->hp;
   dim3 g((nthr + 255) / 256), b(256);
-  if (h->nin == 6) hipLaunchKernelGGL((k_pack<6, 512>), g, b, 0, h->stream, src, h->Wf, h->Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
-  else if (h->nin == 4) hipLaunchKernelGGL((k_pack<4, 320>), g, b, 0, h->stream, src, h->Wf, h->Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
-  else hipLaunchKernelGGL((k_pack<2, 128>), g, b, 0, h->stream, src, h->Wf, h->Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
+  float *Wf = frags ? h->Wf : nullptr, *Wb = frags ? h->Wb : nullptr;
+  if (h->nin == 6) hipLaunchKernelGGL((k_pack<6, 512>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
+  else if (h->nin == 4) hipLaunchKernelGGL((k_pack<4, 320>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
+  else hipLaunchKernelGGL((k_pack<2, 128>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
+}
+
+static LayR layr(const vboc_fit* h) {
+  LayR L;
+  L.nin = h->nin;
+  L.hp = h->hp;
+  L.H = h->hidden;
+  L.b0 = h->hp * h->nin;
+  L.b2 = L.b0 + 3 * h->hp;
+  L.w1 = L.b2 + 4;
+  L.total = h->total;
+  return L;
+}
+
+// P = P * mask and the packed W1 fragments, on the trainer's stream
+static void mask_apply(vboc_fit* h) {
+  hipLaunchKernelGGL(k_mask_apply, dim3((h->total + 255) / 256), dim3(256), 0, h->stream, h->P, h->K, h->Wf, h->Wb,
+                     layr(h));
+}
+
+template <int NIN, int HP>
+static void launch_eval(const EvalArgs& e, int G, hipStream_t s) {
+  hipLaunchKernelGGL((k_eval<NIN, HP>), dim3(G), dim3(256), 0, s, e);
 }
 
 extern "C" {
@@ -824,6 +1123,9 @@ int vboc_fit_create(int nin, int hidden, int minibatch, unsigned long long seed,
   FALLOC(h->part, sizeof(float) * (size_t)(minibatch / R2) * h->rec);
   FALLOC(h->dW1p, sizeof(float) * (size_t)S * hp * hp);
   FALLOC(h->st, sizeof(State));
+  FALLOC(h->K, sizeof(float) * h->total);
+  FALLOC(h->epart, sizeof(double) * 3 * (EVG + 1));
+  FALLOC(h->npruned, sizeof(long long));
 #undef FALLOC
   if ((e = hipHostMalloc((void**)&h->st_host, sizeof(State))) != hipSuccess) return fail_free(e, "hipHostMalloc");
   if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return fail_free(e, "stream");
@@ -836,6 +1138,8 @@ int vboc_fit_create(int nin, int hidden, int minibatch, unsigned long long seed,
   (void)hipMemsetAsync(h->V, 0, sizeof(float) * h->total, h->stream);
   (void)hipMemsetAsync(h->Wf, 0, sizeof(float) * hp * hp, h->stream);
   (void)hipMemsetAsync(h->Wb, 0, sizeof(float) * hp * hp, h->stream);
+  const LayR L = layr(h);
+  hipLaunchKernelGGL(k_mask_ones, dim3((h->total + 255) / 256), dim3(256), 0, h->stream, h->K, L);
   State s{};
   s.seed = seed;
   *h->st_host = s;
@@ -849,12 +1153,14 @@ int vboc_fit_destroy(vboc_fit_handle h) {
   if (!h) return 0;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->exec) (void)hipGraphExecDestroy(h->exec);
-  float* bufs[] = {h->P, h->M, h->V, h->Wf, h->Wb, h->H1p, h->dH2p, h->part, h->dW1p};
+  float* bufs[] = {h->P, h->M, h->V, h->Wf, h->Wb, h->H1p, h->dH2p, h->part, h->dW1p, h->K};
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   for (int* b : h->idx)
     if (b) (void)hipFree(b);
   if (h->st) (void)hipFree(h->st);
+  if (h->epart) (void)hipFree(h->epart);
+  if (h->npruned) (void)hipFree(h->npruned);
   if (h->st_host) (void)hipHostFree(h->st_host);
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   if (h->ev_out) (void)hipEventDestroy(h->ev_out);
@@ -872,6 +1178,7 @@ int vboc_fit_set_params(vboc_fit_handle h, const float* W0, const float* b0, con
   FCHK(hipStreamWaitEvent(h->stream, h->ev_in, 0));
   pack(h, const_cast<float*>(W0), const_cast<float*>(b0), const_cast<float*>(W1), const_cast<float*>(b1),
        const_cast<float*>(W2), const_cast<float*>(b2), 0, h->P);
+  if (h->masked) mask_apply(h);
   FCHK(hipGetLastError());
   FCHK(hipEventRecord(h->ev_out, h->stream));
   FCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0));
@@ -903,7 +1210,7 @@ int vboc_fit_train(vboc_fit_handle h, const vboc_fit_run_t* r, void* stream) {
   const int poll = r->graphs ? (r->poll > 2 ? (r->poll + 1) / 2 * 2 : 2) : (r->poll > 0 ? r->poll : 1);
   Args a;
   memset(&a, 0, sizeof a);
-  a.P = h->P; a.M = h->M; a.V = h->V; a.Wf = h->Wf; a.Wb = h->Wb; a.idx = nullptr;
+  a.P = h->P; a.M = h->M; a.V = h->V; a.K = h->masked ? h->K : nullptr; a.Wf = h->Wf; a.Wb = h->Wb; a.idx = nullptr;
   a.H1p = h->H1p; a.dH2p = h->dH2p; a.part = h->part; a.dW1p = h->dW1p; a.st = h->st;
   a.F = r->F; a.n = r->n; a.n_new = r->n_new; a.ldF = r->ld; a.Bt = h->bt; a.S = h->S; a.lr = (float)r->lr;
   // loop state of the reference: it = 1, val = max |qdot| of the training rows (given by the caller in f64)
@@ -1026,6 +1333,87 @@ int vboc_fit_info(vboc_fit_handle h, int* hidden_padded, int* splits, long long*
   if (splits) *splits = h->S;
   if (adam_steps) *adam_steps = s.step_t;
   if (draws) *draws = s.draws;
+  return 0;
+}
+
+int vboc_fit_set_mask(vboc_fit_handle h, const float* W0, const float* b0, const float* W1, const float* b1,
+                      const float* W2, const float* b2, void* stream) {
+  if (!h) return ffail(VBOC_FIT_EARG, "null handle");
+  const int given = !!W0 + !!b0 + !!W1 + !!b1 + !!W2 + !!b2;
+  if (given != 0 && given != 6) return ffail(VBOC_FIT_EARG, "give all six masks, or none to remove the mask");
+  FCHK(hipEventRecord(h->ev_in, (hipStream_t)stream));
+  FCHK(hipStreamWaitEvent(h->stream, h->ev_in, 0));
+  if (given) {
+    pack(h, const_cast<float*>(W0), const_cast<float*>(b0), const_cast<float*>(W1), const_cast<float*>(b1),
+         const_cast<float*>(W2), const_cast<float*>(b2), 0, h->K, false);
+    mask_apply(h);
+  } else {
+    hipLaunchKernelGGL(k_mask_ones, dim3((h->total + 255) / 256), dim3(256), 0, h->stream, h->K, layr(h));
+  }
+  FCHK(hipGetLastError());
+  h->masked = given != 0;
+  FCHK(hipEventRecord(h->ev_out, h->stream));
+  FCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0));
+  return 0;
+}
+
+int vboc_fit_get_mask(vboc_fit_handle h, float* W0, float* b0, float* W1, float* b1, float* W2, float* b2,
+                      void* stream) {
+  if (!h || !W0 || !b0 || !W1 || !b1 || !W2 || !b2) return ffail(VBOC_FIT_EARG, "null argument");
+  FCHK(hipEventRecord(h->ev_in, (hipStream_t)stream));
+  FCHK(hipStreamWaitEvent(h->stream, h->ev_in, 0));
+  pack(h, W0, b0, W1, b1, W2, b2, 1, h->K);
+  FCHK(hipGetLastError());
+  FCHK(hipEventRecord(h->ev_out, h->stream));
+  FCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0));
+  return 0;
+}
+
+int vboc_fit_prune(vboc_fit_handle h, long long nprune, long long* pruned, void* stream) {
+  if (!h) return ffail(VBOC_FIT_EARG, "null handle");
+  if (h->masked) return ffail(VBOC_FIT_EARG, "a mask is already active (remove it first)");
+  const long long H = h->hidden, n = H * h->nin + H + H * H + H + H + 1;
+  if (nprune < 0 || nprune > n) return ffail(VBOC_FIT_EARG, "nprune outside [0, parameter count]");
+  FCHK(hipEventRecord(h->ev_in, (hipStream_t)stream));
+  FCHK(hipStreamWaitEvent(h->stream, h->ev_in, 0));
+  hipLaunchKernelGGL(k_prune, dim3(1), dim3(PNT), 0, h->stream, h->P, h->K, layr(h), nprune, h->npruned);
+  mask_apply(h);
+  FCHK(hipGetLastError());
+  long long got = -1;
+  FCHK(hipMemcpyAsync(&got, h->npruned, sizeof got, hipMemcpyDeviceToHost, h->stream));
+  FCHK(hipStreamSynchronize(h->stream));
+  h->masked = true;
+  if (pruned) *pruned = got;
+  if (got != nprune) return ffail(VBOC_FIT_EHIP, "the selection pruned " + std::to_string(got) + " entries");
+  FCHK(hipEventRecord(h->ev_out, h->stream));
+  FCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0));
+  return 0;
+}
+
+int vboc_fit_eval(vboc_fit_handle h, const float* F, long long n, int ld, const double* y, float* out,
+                  double* stats, void* stream) {
+  if (!h || !stats) return ffail(VBOC_FIT_EARG, "null argument");
+  if (n < 0 || n >= (1ll << 31)) return ffail(VBOC_FIT_EARG, "rows outside [0, 2^31)");
+  stats[0] = stats[1] = stats[2] = 0.0;
+  if (n == 0) return 0;
+  if (!F) return ffail(VBOC_FIT_EARG, "null argument");
+  if (ld < h->nin + (y ? 0 : 1)) return ffail(VBOC_FIT_EARG, "ld < inputs (+ 1 for the target column)");
+  EvalArgs e;
+  e.P = h->P; e.Wf = h->Wf; e.F = F; e.y = y; e.out = out; e.part = h->epart; e.n = n; e.ld = ld;
+  e.nblk = (int)((n + R2 - 1) / R2);
+  const int G = e.nblk < EVG ? e.nblk : EVG;
+  FCHK(hipEventRecord(h->ev_in, (hipStream_t)stream));
+  FCHK(hipStreamWaitEvent(h->stream, h->ev_in, 0));
+  if (h->nin == 6) launch_eval<6, 512>(e, G, h->stream);
+  else if (h->nin == 4) launch_eval<4, 320>(e, G, h->stream);
+  else launch_eval<2, 128>(e, G, h->stream);
+  double* tot = h->epart + 3 * (size_t)EVG;
+  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, h->stream, h->epart, G, tot);
+  FCHK(hipGetLastError());
+  FCHK(hipMemcpyAsync(stats, tot, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  FCHK(hipStreamSynchronize(h->stream));
+  FCHK(hipEventRecord(h->ev_out, h->stream));
+  FCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0));
   return 0;
 }
 

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvboc_fit.so")
 SRC = os.path.join(HERE, "csrc", "fit.hip")
 EXPORTS = ("vboc_fit_create", "vboc_fit_destroy", "vboc_fit_set_params", "vboc_fit_get_params", "vboc_fit_train",
-           "vboc_fit_sample", "vboc_fit_info", "vboc_fit_last_error")
+           "vboc_fit_sample", "vboc_fit_info", "vboc_fit_last_error", "vboc_fit_set_mask", "vboc_fit_get_mask",
+           "vboc_fit_prune", "vboc_fit_eval")
 EUNSUPPORTED = -3
 
 
@@ -59,6 +60,12 @@ def load():
                                     ctypes.c_void_p, ctypes.c_void_p]
     lib.vboc_fit_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_ulonglong)]
+    lib.vboc_fit_set_mask.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 7
+    lib.vboc_fit_get_mask.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 7
+    lib.vboc_fit_prune.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),
+                                   ctypes.c_void_p]
+    lib.vboc_fit_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
     _lib = lib
     return lib
 

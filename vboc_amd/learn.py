@@ -105,7 +105,7 @@ class DirTrainer:
     (:156-184)."""
 
     def __init__(self, nq, device="cpu", hidden=None, minibatch=None, lr=1e-3, beta=0.95, stop_val=1e-3,
-                 seed=0, graphs=None, poll=64):
+                 seed=0, graphs=None, poll=64, it_max=None):
         self.nq = nq
         self.nin = 2 * nq
         self.device = torch.device(device)
@@ -123,7 +123,7 @@ class DirTrainer:
         self.step_t = torch.zeros((), device=self.device)   # Adam step count (device-side)
         self.graphs = (self.device.type == "cuda") if graphs is None else graphs
         self.poll = poll
-        self.it_max = None
+        self.it_max = it_max      # None: set by the first fit from its dataset (:68-69)
         self.total_steps = 0
         self.seed, self.fits = seed, 0
         # Every buffer a captured step writes or reads across fits is allocated ONCE, here, outside any capture:
@@ -263,6 +263,63 @@ class DirTrainer:
         out = self.predict(F[:, :self.nin])
         return math.sqrt(torch.mean((out - F[:, self.nin:self.nin + 1]) ** 2).item())
 
+    # -- pruning and the safety margin (VBOC/vboc.py:564-642) ------------------------------------------
+    def _prune_targets(self):
+        """(module, name) in the reference's tuple order: the three weights, then the three biases (:566-573)."""
+        st = self.model.linear_relu_stack
+        return [(st[i], name) for name in ("weight", "bias") for i in (0, 2, 4)]
+
+    def n_params(self):
+        return sum(p.numel() for p in self.model.parameters())
+
+    def prune(self, amount=0.5):
+        """prune.global_unstructured(L1Unstructured, amount) over the six tensors (:575-579): the round(amount * n)
+        entries of smallest magnitude are masked.  The `*_orig` parameters are the Parameter objects the trainer
+        already holds (self.params, their .grad buffers, Adam's moments), and the step reaches the masks through
+        the modules' forward pre-hooks, so the next fit() is the reference's refit under the masks (:592-616) with
+        the same optimizer.  Returns the number of entries pruned."""
+        import torch.nn.utils.prune as tprune
+        tprune.global_unstructured(self._prune_targets(), pruning_method=tprune.L1Unstructured, amount=amount)
+        return int(sum(int((m == 0).sum()) for m in self.masks()))
+
+    def prune_remove(self):
+        """prune.remove on the six tensors (:620-625): the masks go, the zeros stay, and a later fit trains every
+        parameter again.  Adam's moments keep their positions."""
+        import torch.nn.utils.prune as tprune
+        for mod, name in self._prune_targets():
+            if hasattr(mod, name + "_mask"):
+                tprune.remove(mod, name)
+        self.params = [p for p in self.model.parameters()]
+        for p in self.params:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+
+    def masks(self):
+        """The six 0 / 1 masks in parameter order (W0, b0, W1, b1, W2, b2); all ones when nothing is pruned."""
+        st = self.model.linear_relu_stack
+        out = []
+        for i in (0, 2, 4):
+            for name in ("weight", "bias"):
+                m = getattr(st[i], name + "_mask", None)
+                ref = getattr(st[i], name)
+                out.append(m.detach().clone() if m is not None else torch.ones_like(ref))
+        return out
+
+    def safety_margin(self, F):
+        """max (out_i - y_i) / y_i over the rows of F ([n, 2nq+1] features) with out_i > y_i (VBOC/vboc.py:638-642):
+        out is the float32 model output, the ratio is formed in float64 from the target as given (float64 for a
+        float64 array).  A fraction; Safe MPC's `safety_margin` option is a percentage, 100 times this.  The
+        reference raises when no output exceeds its target (np.amax of an empty array); here that case is 0.0."""
+        if torch.is_tensor(F):
+            y = F[:, self.nin].detach().cpu().double().numpy()
+        else:
+            y = np.asarray(F)[:, self.nin].astype(np.float64)
+        X = F[:, :self.nin] if torch.is_tensor(F) else np.asarray(F)[:, :self.nin]
+        out = self.predict(X).reshape(-1).cpu().double().numpy()
+        d = out - y
+        over = d > 0
+        return float(np.max(d[over] / y[over])) if over.any() else 0.0
+
 
 class HipTrainer(DirTrainer):
     """DirTrainer's fit on the device kernels of csrc/fit.hip (libvboc_fit.so, include/vboc_fit.h): sampling,
@@ -274,11 +331,11 @@ class HipTrainer(DirTrainer):
     and val, kept in float64 as the reference's Python float."""
 
     def __init__(self, nq, device="cuda", hidden=None, minibatch=None, lr=1e-3, beta=0.95, stop_val=1e-3, seed=0,
-                 graphs=True, poll=64):
+                 graphs=True, poll=64, it_max=None):
         import ctypes
         from . import fitlib
         super().__init__(nq, device, hidden=hidden, minibatch=minibatch, lr=lr, beta=beta, stop_val=stop_val,
-                         seed=seed, graphs=False, poll=poll)
+                         seed=seed, graphs=False, poll=poll, it_max=it_max)
         if self.device.type != "cuda":
             raise ValueError("HipTrainer runs on a GPU (use DirTrainer on the CPU)")
         self._fl = fitlib
@@ -334,6 +391,78 @@ class HipTrainer(DirTrainer):
         self.total_steps += launched.value
         self.last = dict(iterations=its.value, val=val.value, launched=launched.value, fit_ms=ms.value)
         return dict(iterations=its.value, val=val.value, launched=launched.value)
+
+    # -- pruning: the mask lives in the native trainer, the torch module stays plain ----------------------
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def prune(self, amount=0.5):
+        """DirTrainer.prune on the device (vboc_fit_prune): the round(amount * n) entries of smallest magnitude
+        (Python's round, as torch's) are selected by a radix select over the packed parameters, masked and zeroed;
+        the zeros are written back to the module.  Ties at the threshold magnitude go in the order W0, b0, b1, W2,
+        b2, W1, row-major in each (torch's own tie choice is unspecified).  Until prune_remove() every fit masks
+        the gradient and holds the pruned entries at zero.  Returns the number of entries pruned."""
+        import ctypes
+        k = round(amount * self.n_params())
+        ptrs = self._param_ptrs()
+        self._fl.check(self._lib.vboc_fit_set_params(self._h, *ptrs, self._stream()))
+        got = ctypes.c_longlong()
+        self._fl.check(self._lib.vboc_fit_prune(self._h, k, ctypes.byref(got), self._stream()))
+        self._fl.check(self._lib.vboc_fit_get_params(self._h, 0, *ptrs, self._stream()))
+        return got.value
+
+    def set_mask(self, masks=None):
+        """Make the six 0 / 1 tensors (parameter order) the mask, or remove the mask (None).  The module's masked
+        entries are zeroed as the trainer's are."""
+        ptrs = self._param_ptrs()
+        if masks is None:
+            self._fl.check(self._lib.vboc_fit_set_mask(self._h, *([None] * 6), self._stream()))
+            return
+        ms = [m.to(self.device, torch.float32).contiguous() for m in masks]
+        if [tuple(m.shape) for m in ms] != [tuple(p.shape) for p in self.model.parameters()]:
+            raise ValueError("masks must have the parameters' shapes")
+        self._fl.check(self._lib.vboc_fit_set_params(self._h, *ptrs, self._stream()))
+        self._fl.check(self._lib.vboc_fit_set_mask(self._h, *[m.data_ptr() for m in ms], self._stream()))
+        self._fl.check(self._lib.vboc_fit_get_params(self._h, 0, *ptrs, self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()     # `ms` must outlive the copy
+
+    def prune_remove(self):
+        self.set_mask(None)
+
+    def masks(self):
+        ts = [torch.empty_like(p) for p in self.model.parameters()]
+        self._fl.check(self._lib.vboc_fit_get_mask(self._h, *[t.data_ptr() for t in ts], self._stream()))
+        return ts
+
+    def evaluate(self, F):
+        """Forward-only pass of the module's current parameters over the feature rows F ([n, 2nq+1]) on the device
+        kernel (vboc_fit_eval, the training forward's arithmetic): dict(rmse, safety_margin, over, out) with
+        rmse = sqrt(mean (out - y)^2) accumulated in float64, the safety margin of DirTrainer.safety_margin, the
+        count of rows with out > y, and out the [n, 1] float32 outputs.  The target is the float64 column when F is
+        a float64 array, else the float32 one promoted.  Fixed-order reductions: repeated calls return the same
+        bits."""
+        import ctypes
+        y = None
+        if torch.is_tensor(F):
+            Ft = F.to(self.device, torch.float32).contiguous()
+            if F.dtype == torch.float64:
+                y = F[:, self.nin].to(self.device).contiguous()
+        else:
+            Fn = np.asarray(F)
+            Ft = torch.as_tensor(Fn, dtype=torch.float32).to(self.device).contiguous()
+            if Fn.dtype == np.float64:
+                y = torch.as_tensor(np.ascontiguousarray(Fn[:, self.nin])).to(self.device)
+        n = Ft.shape[0]
+        out = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+        stats = (ctypes.c_double * 3)()
+        self._fl.check(self._lib.vboc_fit_set_params(self._h, *self._param_ptrs(), self._stream()))
+        ptr = lambda t: t.data_ptr() if (t is not None and n) else None
+        self._fl.check(self._lib.vboc_fit_eval(self._h, ptr(Ft), n, Ft.shape[1], ptr(y), ptr(out), stats,
+                                               self._stream()))
+        return dict(rmse=math.sqrt(stats[0] / n) if n else 0.0, safety_margin=stats[1], over=int(stats[2]), out=out)
+
+    def safety_margin(self, F):
+        return self.evaluate(F)["safety_margin"]
 
     def moments(self):
         """Adam's (exp_avg, exp_avg_sq) as lists of tensors in the model's parameter order (test hook)."""

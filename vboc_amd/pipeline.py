@@ -38,8 +38,9 @@ def samples_array(nq, results):
     return np.array(rows, dtype=np.float64).reshape(len(rows), 2 * nq)
 
 
-def save_artifacts(out_dir, nq, X_save, mean, std, model, times, rmse):
-    """The reference's file names and formats (VBOC/triplependulum_vboc.py:51-52,204-215)."""
+def save_artifacts(out_dir, nq, X_save, mean, std, model, times, rmse, margin=None):
+    """The reference's file names and formats (VBOC/triplependulum_vboc.py:51-52,204-215); margin (the safety
+    margin of VBOC/vboc.py:638-642, a fraction) goes to margin_<n>dof_vboc as torch.save of a float."""
     import torch
     os.makedirs(out_dir, exist_ok=True)
     tag = f"{nq}dof_vboc"
@@ -49,17 +50,22 @@ def save_artifacts(out_dir, nq, X_save, mean, std, model, times, rmse):
     torch.save(mean, os.path.join(out_dir, f"mean_{tag}"))
     torch.save(std, os.path.join(out_dir, f"std_{tag}"))
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(out_dir, f"model_{tag}"))
+    if margin is not None:
+        torch.save(float(margin), os.path.join(out_dir, f"margin_{tag}"))
 
 
 def load_artifacts(out_dir, nq, device="cpu"):
-    """Read the artefacts back the way triplependulum_comparison.py:31-36 does (weights_only loads)."""
+    """Read the artefacts back the way triplependulum_comparison.py:31-36 does (weights_only loads); `margin` is
+    None when the run saved none."""
     import torch
     from .learn import NeuralNetDIR
     tag = f"{nq}dof_vboc"
     sd = torch.load(os.path.join(out_dir, f"model_{tag}"), weights_only=True)
     model = NeuralNetDIR(2 * nq, sd["linear_relu_stack.0.weight"].shape[0], 1).to(device)
     model.load_state_dict(sd)
-    return dict(model=model, data=np.load(os.path.join(out_dir, f"data_{tag}.npy")),
+    mpath = os.path.join(out_dir, f"margin_{tag}")
+    margin = torch.load(mpath, weights_only=True) if os.path.exists(mpath) else None
+    return dict(model=model, margin=margin, data=np.load(os.path.join(out_dir, f"data_{tag}.npy")),
                 mean=torch.load(os.path.join(out_dir, f"mean_{tag}"), weights_only=True),
                 std=torch.load(os.path.join(out_dir, f"std_{tag}"), weights_only=True),
                 times=np.load(os.path.join(out_dir, f"times_{tag}.npy")),
@@ -291,6 +297,19 @@ class SegmentedProducer:
                     waited_s=sum(i["waited_s"] for i in infos))
 
 
+def prune_and_refit(trainer, F, F_test, amount, it_max=None, log=None):
+    """The reference's steps after the last fit (VBOC/vboc.py:564-635): global L1 prune of `amount` over the six
+    tensors, a refit on the whole set under the masks (same optimizer, val reset, it from 1), prune.remove, the
+    RMSE on the test set.  Returns dict(amount, pruned, fit, rmse)."""
+    pruned = trainer.prune(amount)
+    fit = trainer.fit(F, it_max=it_max)
+    trainer.prune_remove()
+    rmse = trainer.rmse(F_test)
+    if log:
+        log(f"pruned {pruned} of {trainer.n_params()} parameters: refit {fit}, rmse {rmse:.4g}")
+    return dict(amount=amount, pruned=pruned, fit=fit, rmse=rmse)
+
+
 def _agree(flag):
     """Rank 0's decision on every rank (the time budget must not split the ranks' loop counts)."""
     import torch
@@ -306,8 +325,14 @@ def _agree(flag):
 
 def vboc_run(nq, backend, X_test, stop_time, num_prob=1000, max_iterations=None, N_start=None, seed=SEED,
              out_dir=None, device=None, trainer_kw=None, triple_refit_quirk=True, log=None, stream=None,
-             stream_rounds=None, segment_factory=None):
-    """Run the VBOC loop; returns dict(X_save, mean, std, trainer, times, rmse, stats).
+             stream_rounds=None, segment_factory=None, prune_amount=None):
+    """Run the VBOC loop; returns dict(X_save, mean, std, trainer, times, rmse, stats, fits, producer, prune,
+    safety_margin).
+    prune_amount (VBOC/vboc.py:564-642; default None: no pruning): after the last refit, rank 0 prunes that share of
+    the parameters, refits on the whole set and removes the masks (prune_and_refit; `prune` = dict(amount, pruned,
+    fit, rmse), else None); the saved model is the pruned one.  safety_margin is the trainer's on the held-out set
+    after that, a fraction (Safe MPC's option of that name is a percentage, 100 times it); with out_dir it is also
+    written to margin_<n>dof_vboc.
     stream (default: on the GPU backend): the iterations' data generation runs as producer launches ahead of the
     fits (StreamedRounds), each over stream_rounds iterations (default: max_iterations + 1, else 64, capped by the
     row-pool budget STREAM_POOL_BYTES); when the loop passes a launch's last iteration the next launch starts
@@ -375,10 +400,16 @@ def vboc_run(nq, backend, X_test, stop_time, num_prob=1000, max_iterations=None,
     finally:
         # an exception anywhere above must not leave a producer launch running on the handle
         producer_info = producer.close(cancel=True) if producer is not None else None
+    pruned, margin = None, None
+    if rank0:
+        if prune_amount is not None:
+            pruned = prune_and_refit(trainer, F, F_test, prune_amount, log=log)
+        margin = trainer.safety_margin(F_test)
+        log(f"safety margin {margin:.4g}")
     if rank0 and out_dir is not None:
-        save_artifacts(out_dir, nq, X_save, mean, std, trainer.model, times, rmse)
+        save_artifacts(out_dir, nq, X_save, mean, std, trainer.model, times, rmse, margin=margin)
     return dict(X_save=X_save, mean=mean, std=std, trainer=trainer, times=times, rmse=rmse, stats=stats, fits=fits,
-                producer=producer_info)
+                producer=producer_info, prune=pruned, safety_margin=margin)
 
 
 def pendulum_vboc_run(out_dir=None, device="cuda", seed=0, backend=None, it_max=None):
@@ -480,7 +511,7 @@ def ur5_run(backend=None, num_test=10000, num_train=100000, out_dir=None, device
 
 
 def cartesian_run(backend=None, num_test=1000, num_train=100000, out_dir=None, device="cuda", seed=0,
-                  minibatch=4096, hidden=300, log=None):
+                  minibatch=4096, hidden=300, log=None, prune_amount=None, trainer_kw=None):
     """The main block of VBOC/Cartesian constraints/vboc_multiprocessing.py (double pendulum with the end-effector
     keep-out circle), on one GPU or sharded over the ranks of torch.distributed like ur5_run:
       test set      `testing_test` over ids [0, num_test) (:557-562)
@@ -492,8 +523,11 @@ def cartesian_run(backend=None, num_test=1000, num_train=100000, out_dir=None, d
                     EMA beta 0.95, stop at val <= 1e-3 or it_max = 100 * int(n * 100 / 4096) steps (:617-660), on
                     the HIP-graph trainer
       RMSE          on the training and the test data (:662-690); artefacts model_/mean_/std_2dof_vboc_10_300.
+      pruning       with prune_amount: the global L1 prune, the refit under the masks and prune.remove of the
+                    reference's main block (prune_and_refit); the safety margin on the test set (a fraction)
+                    is always computed and written to margin_2dof_vboc_10_300
     backend: a drivers backend carrying the circle (default: GpuBackend(2, path_constraint=...)).  Returns
-    dict(X_test, X_train, fit, rmse_train, rmse_test, stats)."""
+    dict(X_test, X_train, fit, rmse_train, rmse_test, stats, prune, safety_margin)."""
     import torch
     from .drivers import GpuBackend, cartesian_testing_batch, cartesian_testing_device
     from .systems import cartesian_constraint
@@ -519,11 +553,16 @@ def cartesian_run(backend=None, num_test=1000, num_train=100000, out_dir=None, d
     F = dir_features(X_train, mean, std, 2)
     F_test = dir_features(X_test, mean, std, 2)
     k = min(minibatch, F.shape[0])
-    tr = make_trainer(2, device=device, hidden=hidden, minibatch=k, beta=0.95, stop_val=1e-3, seed=seed)
+    tr = make_trainer(2, device=device, hidden=hidden, minibatch=k, beta=0.95, stop_val=1e-3, seed=seed,
+                      **(trainer_kw or {}))
     B = int(F.shape[0] * 100 / k)
     fit = tr.fit(F, it_max=max(1, B * 100))
     rmse_train, rmse_test = tr.rmse(F), tr.rmse(F_test)
     log(f"fit {fit}  RMSE train {rmse_train:.4g} test {rmse_test:.4g}")
+    pruned = None
+    if prune_amount is not None:
+        pruned = prune_and_refit(tr, F, F_test, prune_amount, it_max=max(1, B * 100), log=log)
+    margin = tr.safety_margin(F_test)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         tag = f"2dof_vboc_10_{hidden}"
@@ -531,5 +570,6 @@ def cartesian_run(backend=None, num_test=1000, num_train=100000, out_dir=None, d
         torch.save({kk: v.detach().cpu() for kk, v in tr.model.state_dict().items()}, os.path.join(out_dir, "model_" + tag))
         torch.save(mean, os.path.join(out_dir, "mean_" + tag))
         torch.save(std, os.path.join(out_dir, "std_" + tag))
+        torch.save(float(margin), os.path.join(out_dir, "margin_" + tag))
     return dict(X_test=X_test, X_train=X_train, fit=fit, rmse_train=rmse_train, rmse_test=rmse_test,
-                stats=(st_test, st_train), mean=mean, std=std)
+                stats=(st_test, st_train), mean=mean, std=std, prune=pruned, safety_margin=margin)
