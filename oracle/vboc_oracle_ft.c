@@ -56,6 +56,13 @@
 
 #include "vboc_oracle.h"
 
+/* The line search accepts a step whose merit is below phi0 (1 + VBOC_FT_LS_EPS).  0 (the default, and every shipped
+   build): the plain comparison pa < phi0, bit for bit.  tools/trunc_spread_ft.py builds the oracle with +-1e-15 to find the
+   problems whose line search is decided by rounding (an iterate that has converged in x, u while its multipliers lag). */
+#ifndef VBOC_FT_LS_EPS
+#define VBOC_FT_LS_EPS 0.0
+#endif
+
 #define FQ 3
 #define FX (2 * FQ + 1)
 #define FU FQ
@@ -1058,7 +1065,7 @@ static void fsqp(fprob_t* P, vboc_result_t* res) {
       const double phi0 = fmerit(P, 0.0);
       for (;;) {
         const double pa = fmerit(P, alpha);
-        if (pa < phi0) break;
+        if (pa < phi0 * (1.0 + VBOC_FT_LS_EPS)) break;
         if (alpha * o->alpha_reduction < o->alpha_min) break;
         alpha *= o->alpha_reduction;
       }

@@ -143,31 +143,52 @@ def _child(out):
     np.savez(out, **save)
 
 
+def run_variants(tmp, script, variants=None):
+    """Copy oracle/ into tmp once per flag set of `variants` (default VARIANTS), build it, and run `script --child OUT.npz` on each build
+    (VBOC_ORACLE_LIB).  Returns ({variant: the npz}, [the variants that do not build])."""
+    runs, skipped = {}, []
+    for name, flags in variants or VARIANTS:
+        d = os.path.join(tmp, name)
+        shutil.copytree(os.path.join(ROOT, "oracle"), os.path.join(d, "oracle"),
+                        ignore=shutil.ignore_patterns("*.so", "__pycache__", "_ref"))
+        os.makedirs(os.path.join(d, "vboc_amd", "csrc"))     # vboc_oracle.c includes the arm's parameters from there
+        shutil.copy(os.path.join(ROOT, "vboc_amd", "csrc", "ur5_params.h"), os.path.join(d, "vboc_amd", "csrc"))
+        mk = subprocess.run(["make", "-s", "-C", os.path.join(d, "oracle"), f"CFLAGS={flags}"],
+                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if mk.returncode != 0:
+            if name == "committed":
+                raise RuntimeError(mk.stdout)
+            skipped.append(name)
+            print(f"variant {name} does not build, skipped:\n{mk.stdout[-400:]}", file=sys.stderr)
+            continue
+        npz = os.path.join(d, "out.npz")
+        env = dict(os.environ, VBOC_ORACLE_LIB=os.path.join(d, "oracle", "libvboc_oracle.so"))
+        subprocess.check_call([sys.executable, os.path.abspath(script), "--child", npz], env=env)
+        runs[name] = np.load(npz)
+    return runs, skipped
+
+
+def write_fixture(out, fx):
+    """The fixture as JSON, one line per group and cut."""
+    with open(out, "w") as f:
+        head = {k: v for k, v in fx.items() if k != "groups"}
+        f.write("{\n" + "".join(f" {json.dumps(k)}: {json.dumps(v)},\n" for k, v in head.items()))
+        f.write(' "groups": {\n')
+        for i, (gk, e) in enumerate(fx["groups"].items()):
+            f.write(f"  {json.dumps(gk)}: {{\n")
+            f.write("".join(f"   {json.dumps(k)}: {json.dumps(v)},\n" for k, v in e.items() if k != "cuts"))
+            cuts = ",\n".join(f"    {json.dumps(ck)}: {json.dumps(cv)}" for ck, cv in e["cuts"].items())
+            f.write('   "cuts": {\n' + cuts + "\n   }\n  }" + ("," if i + 1 < len(fx["groups"]) else "") + "\n")
+        f.write(" }\n}\n")
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "--child":
         return _child(sys.argv[2])
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else FIXTURE
     tmp = tempfile.mkdtemp(prefix="trunc_spread_")
     try:
-        runs, skipped = {}, []
-        for name, flags in VARIANTS:
-            d = os.path.join(tmp, name)
-            shutil.copytree(os.path.join(ROOT, "oracle"), os.path.join(d, "oracle"),
-                            ignore=shutil.ignore_patterns("*.so", "__pycache__", "_ref"))
-            os.makedirs(os.path.join(d, "vboc_amd", "csrc"))     # vboc_oracle.c includes the arm's parameters from there
-            shutil.copy(os.path.join(ROOT, "vboc_amd", "csrc", "ur5_params.h"), os.path.join(d, "vboc_amd", "csrc"))
-            mk = subprocess.run(["make", "-s", "-C", os.path.join(d, "oracle"), f"CFLAGS={flags}"],
-                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            if mk.returncode != 0:
-                if name == "committed":
-                    raise RuntimeError(mk.stdout)
-                skipped.append(name)
-                print(f"variant {name} does not build, skipped:\n{mk.stdout[-400:]}", file=sys.stderr)
-                continue
-            npz = os.path.join(d, "out.npz")
-            env = dict(os.environ, VBOC_ORACLE_LIB=os.path.join(d, "oracle", "libvboc_oracle.so"))
-            subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", npz], env=env)
-            runs[name] = np.load(npz)
+        runs, skipped = run_variants(tmp, __file__)
         base = runs["committed"]
         fx = dict(cuts=[list(c) for c in CUTS], tol_factor=TOL_FACTOR, drop_cap=DROP_CAP,
                   variants={n: f for n, f in VARIANTS if n in runs}, skipped_variants=skipped, groups={})
@@ -194,16 +215,7 @@ def main():
                                                sqp_iter=get(base, cut, "sqp_iter").tolist(),
                                                qp_iter=get(base, cut, "qp_iter").tolist(), spread=spread)
             fx["groups"][group_key(g)] = e
-        with open(out, "w") as f:      # one line per group and cut
-            head = {k: v for k, v in fx.items() if k != "groups"}
-            f.write("{\n" + "".join(f" {json.dumps(k)}: {json.dumps(v)},\n" for k, v in head.items()))
-            f.write(' "groups": {\n')
-            for i, (gk, e) in enumerate(fx["groups"].items()):
-                f.write(f"  {json.dumps(gk)}: {{\n")
-                f.write("".join(f"   {json.dumps(k)}: {json.dumps(v)},\n" for k, v in e.items() if k != "cuts"))
-                cuts = ",\n".join(f"    {json.dumps(ck)}: {json.dumps(cv)}" for ck, cv in e["cuts"].items())
-                f.write('   "cuts": {\n' + cuts + "\n   }\n  }" + ("," if i + 1 < len(fx["groups"]) else "") + "\n")
-            f.write(" }\n}\n")
+        write_fixture(out, fx)
         for name in dict.fromkeys(s[0] for s in SYSTEMS):
             print(name, " ".join(f"{cut_key(c)}: {tol(fx, name, c) / TOL_FACTOR:.1e}" for c in CUTS))
     finally:

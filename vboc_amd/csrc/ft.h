@@ -481,11 +481,17 @@ struct Ft {
       }
       return c;
     }
-    for (int k = t; k < sh.N; k += 64) {
-      const double* r = rec(k);
-      for (int i = 0; i < NX; ++i) c += (k == 0 ? sh.c0[i] : sh.cp[i]) * r[L::X + i];
+    // the free-time cost in the oracle's order (fcost: stage by stage, no contraction) on every lane, so that equal
+    // iterates give the oracle's cost to the last bit; a sum across lanes differs from it in the last digits from
+    // N = 63 on (once per solve: N + 1 uniform record reads)
+    {
+#pragma clang fp contract(off)
+      for (int k = 0; k < sh.N; ++k) {
+        const double* r = rec(k);
+        for (int i = 0; i < NX; ++i) c += (k == 0 ? sh.c0[i] : sh.cp[i]) * r[L::X + i];
+      }
     }
-    return ft_wsum(c);
+    return c;
   }
 
   __device__ void store(const Inputs& in, int status, int it, int qit) {
