@@ -56,9 +56,31 @@ __host__ __device__ constexpr int even_up(int v) { return (v + 1) & ~1; }
 #endif
 __host__ __device__ constexpr int rec_up(int v) { return (v + VBOC_REC_ALIGN - 1) / VBOC_REC_ALIGN * VBOC_REC_ALIGN; }
 
-template <int NQ>
+// Build-time selectors that also decide the stage-record order (documented where the passes use them, below)
+#ifndef VBOC_FUSE
+#define VBOC_FUSE 127
+#endif
+#ifndef VBOC_ACL_FUSED_NQ
+#define VBOC_ACL_FUSED_NQ (1 << 3)
+#endif
+#ifndef VBOC_RINV
+#define VBOC_RINV 1
+#endif
+// LDS-vector mask of an instantiation (round 8, bits 32.. of VBOC_FUSE shifted down; see the pass fusions below):
+// only the kernels that run every fusion of rounds 5-7, i.e. the triple with the MFMA factorisation and no path
+// constraint.  0 for every other instantiation, and for every instantiation with -DVBOC_FUSE=31.
+__host__ __device__ constexpr int lds_vec_mask(int nq, bool fm, bool hc) {
+  return (nq == 3 && fm && !hc && (VBOC_FUSE & 31) == 31 && ((VBOC_ACL_FUSED_NQ >> 3) & 1) && VBOC_RINV) ? ((VBOC_FUSE >> 5) & 3)
+                                                                                                        : 0;
+}
+
+// LV: the per-stage vectors that travel through LDS rows instead of the stage record (lds_vec_mask; 1: C, 2: k_f).
+// The record order may depend on the kernel instantiation: records are private to one kernel during a job (kernels
+// exchange state through Work / SlotState).
+template <int NQ, int LV = 0>
 struct WaveLayout {
   static constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, M0 = NQ + 1;
+  static constexpr bool C_LDS = LV & 1, K_LDS = LV & 2;
   // global stage record: A, B, e (defect -> initial residual), D (H / g_corr / corrector direction), DA (g_pred /
   // affine direction / costate), z (current iterate), dz, lambda_l, lambda_u, K, k_f, chol(Ru) (Ru^-1), M, Y, P e, C,
   // A_cl, then the SQP state x, u, pi, lam_l, lam_u, w_pi.  IN_FIRST (the pendulum chains, since round 6): the
@@ -70,9 +92,12 @@ struct WaveLayout {
                        ODA = OD + NZ, OZ = IN_FIRST ? ODA + NZ : P0, ODZ = OZ + NZ, OQL = ODZ + NZ, OQU = OQL + NZ,
                        OK = P0 + 6 * NZ + NX, OKF = OK + NU * NX,
                        OLR = IN_FIRST ? OKF + NU + NU * NQ : OKF + NU, OM = IN_FIRST ? OKF + NU : OLR + NU * NU,
-                       OY = OKF + NU + NU * NU + NU * NQ, OPE = OY + NU * NQ, OC = OPE + NX,
-                       OACL = OC + NX, OX = OACL + NX * NX, OU = OX + NX, OPI = OU + NU, OLL = OPI + NX,
-                       OLU = OLL + NZ, OWPI = OLU + NZ, REC = rec_up(OWPI + NX);
+                       OY = OKF + NU + NU * NU + NU * NQ, OPE = OY + NU * NQ, OC = C_LDS ? OPE + NX + NX * NX : OPE + NX,
+                       OACL = C_LDS ? OPE + NX : OC + NX, OX = OPE + 2 * NX + NX * NX, OU = OX + NX, OPI = OU + NU,
+                       OLL = OPI + NX, OLU = OLL + NZ, OWPI = OLU + NZ, REC = rec_up(OWPI + NX);
+  // C_LDS: the sweeps' constant C lives in the staging rows XS, its record field is dead and sits behind A_cl, so the
+  // hot stream [0, HOT) that every IPM iteration moves (and the resident-problem budget is sized from) ends at A_cl
+  static constexpr int HOT = C_LDS ? OC : OX;
   static_assert((IN_FIRST ? OQU : ODA) + NZ == OK, "the fields before K are A, B, e, D, DA, z, dz, lambda_l, lambda_u");
   // IN_FIRST also puts M before chol(Ru): the forward sweep's constant pass reads [k_f, M] and the vector pass's k_f
   // pass [chol(Ru), Y], each one contiguous range without the other's field
@@ -83,8 +108,10 @@ struct WaveLayout {
   // [OPE, OX); forward sweep [OC, OX); costate [0, W_COS): A (and B) to the end of lambda_u
   // W_FINV: the inputs and DA, the predictor gradient (VFUSE, the triple: the factorisation also runs the predictor's
   // vector step; 78 doubles, still one LDS-DMA)
-  static constexpr int W_FAC = OC, W_FIN = even_up(ODA), W_FINV = even_up(ODA + NZ), LO_VEC = OPE, W_VEC = OX - OPE,
-                       LO_FWD = OC, W_FWD = OX - OC, W_COS = even_up(OQU + NZ);
+  // C_LDS: the vector pass's window is [P e | A_cl] = [OPE, HOT), the forward sweep's [A_cl] = [OACL, HOT); the
+  // factorisation writes back [OK, HOT)
+  static constexpr int W_FAC = OPE + NX, W_FIN = even_up(ODA), W_FINV = even_up(ODA + NZ), LO_VEC = OPE,
+                       W_VEC = HOT - OPE, LO_FWD = C_LDS ? OACL : OC, W_FWD = HOT - LO_FWD, W_COS = even_up(OQU + NZ);
   // LDS-DMA rings (global_load_lds_dwordx4: one wave-instruction lands 64 lanes x 16 B = 128 doubles):
   // the factorisation streams its window two stages ahead through 4 slots of 2 KiB (two DMAs per
   // stage), the vector / forward / costate recursions six stages ahead through 8 slots of 1 KiB
@@ -115,11 +142,21 @@ struct WaveLayout {
                        PE0 = Y0 + M0 * NQ, P = PE0 + NX, PA = P + NX * NX, PB = PA + NX * NX, APA = PB + NX * NU,
                        RU = APA + NX * NX, S = RU + NU * NU, PI = S + NU * NX, PV = PI + NX * NQ, DXV = PV + 2 * NX,
                        SC = DXV + 2 * NX, LINE = SC + NQ * NQ, ZERO = LINE + NQ, TRASH = ZERO + 16, PAR = TRASH + 64,
-                       XS = even_up(PAR + Par<NQ>::COUNT);
+                       HU = even_up(PAR + Par<NQ>::COUNT), XS = K_LDS ? HU + 128 : HU;
+  // HU: factor_mfma's H_u image [8][16].  It lies on the first staging rows, which are free during the
+  // factorisation - unless the rows also carry k_f (K_LDS: the factorisation's vector step writes them), then it
+  // has 128 doubles of its own in front of them.
+  // XR: row stride.  K_LDS: a row is [v / dx / costate (NX) | k_f, then k_f - M nu (NU) | pad], 16-B aligned
+  static constexpr int XR = K_LDS ? even_up(NX + NU) : NX, XKF = NX;
   // XS: per-stage staging rows [nmax + 1][NX] (v of the vector pass, dx of the forward sweep, the
   // costate) so that the recursions issue no global stores
   static_assert(M0 * NX <= NX * NX, "stage-0 B'P reuses the PA scratch");
-  static constexpr size_t lds_bytes(int nmax) { return ((size_t)XS + (size_t)(nmax + 1) * NX) * sizeof(double); }
+  // C_LDS: the rows also carry the sweeps' constants (c_k in row k + 1 of the forward sweeps, c'_k in row k of the
+  // corrector's vector sweep, each overwritten by the step that consumes it); the top partial group loads rows past
+  // stage N - 1 (never used in arithmetic), so the rows get the region's SLACK
+  static constexpr size_t lds_bytes(int nmax) {
+    return ((size_t)XS + (size_t)(nmax + 1 + (C_LDS ? SLACK : 0)) * XR) * sizeof(double);
+  }
   static constexpr size_t region_doubles(int nmax) { return (size_t)REC * (nmax + 1 + SLACK); }
 };
 
@@ -324,9 +361,21 @@ __device__ unsigned long long g_wave_prof[16];
 //            factor_mfma one stage behind the matrix recursion, on the ring slot that holds all its operands; k_f
 //            goes to the record with the stage's write-back.  vec<ODA> keeps only the lin = sum Y'k_f pass and
 //            stage 0.  Per row the operations and their order are those of vec (bit-identical).
-#ifndef VBOC_FUSE
-#define VBOC_FUSE 31
-#endif
+//  32 CLDS   (round 8; the VFUSE instantiations with all of 1-16 on) the sweeps' constant C travels between the
+//            passes of one wave through the staging rows XS instead of the stage record: the forward sweeps' constant
+//            pass writes c_k into row k + 1 and step k reads it there before storing dx_{k+1} over it; prep_corr writes
+//            c'_k into row k for the corrector's vector sweep, whose step k stores v_k over it.  The record keeps a dead
+//            C field behind A_cl (WaveLayout's LV order): the forward window is [A_cl], the vector window [P e | A_cl]
+//            (three stages per DMA instead of two) and the factorisation's write-back ends at A_cl.  Same operations
+//            in the same order on the same values (bit-identical).  -DVBOC_FUSE=31: round 7's passes and record.
+//  64 KLDS   (round 8, same instantiations) k_f, then k_f - M nu, lives in three more words of stage k's staging row
+//            (row stride XR): written by vstep (predictor) and by the corrector's k_f pass, read by the lin pass and the
+//            forward sweeps' constant pass, which stores k_f - M nu over it for the step-length pass.  The record's k_f
+//            field stays where it is (the write-back carries stale words there) but no pass loads or stores it: the
+//            constant pass loads M alone, the step-length pass K alone.  factor_mfma's H_u image, which lay on the
+//            first rows, gets 128 doubles of its own.  Bit-identical.
+//            Both bits apply to k_dg / k_ts only: k_wave<3, true> keeps round 7's passes (see the note at its end).
+// (the default, 127, is set in front of WaveLayout: the mask also decides the record order)
 
 // HC: the Cartesian path-constraint rows (vboc_set_path_constraint; oracle/vboc_oracle.c hc_*, Lane::hc_*) on
 // stages 1..N-1, pendulum chains with the VALU factorisation only.  No change of the stage-record layout: the
@@ -334,9 +383,13 @@ __device__ unsigned long long g_wave_prof[16];
 // block diag(H_q) + sigma c c' travels to the factorisation in the K field of the record (free between
 // prep_pred and the factorisation step that writes K), and the costate's c (lambda_u - lambda_l) term in the
 // B field (free once the QP has finished).
-template <int NQ, bool FM = false, bool HC = false>
+template <int NQ, bool FM = false, bool HC = false, int LV = lds_vec_mask(NQ, FM, HC)>
 struct Coop {
-  using L = WaveLayout<NQ>;
+  using L = WaveLayout<NQ, LV>;
+  static constexpr bool CLDS = L::C_LDS, KLDS = L::K_LDS;
+  static constexpr int XR = L::XR;   // stride of the staging rows
+  // KLDS: k_f (then k_f - M nu) of stage k, in its staging row
+  __device__ __forceinline__ double& kfr(int k, int a) const { return s[L::XS + k * XR + L::XKF + a]; }
   using HL = Lane<NQ>;
   static_assert(!HC || (!FM && NQ >= 2 && NQ <= 3), "path constraint: pendulum chains, VALU factorisation");
   using PF = Par<NQ>;
@@ -1149,13 +1202,11 @@ struct Coop {
   // inside an MFMA differs (rounding-level).
   static constexpr int CE = NX + NU, CP = CE + 1;   // H row / G column of rs e; first Pi column
   // A_cl = A + B K of stages N-1..1 is formed inside factor_mfma (acl_slot) and written back with the
-  // stage's outputs (ring_wb<OK, OX>: K .. Pe, C (dead until vec rebuilds it), A_cl): no acl_pass re-reading A, B
+  // stage's outputs (ring_wb<OK, HOT>: K .. Pe, C (dead until vec rebuilds it; CLDS: not at all), A_cl): no acl_pass re-reading A, B
   // and K from the stage records.  Per chain (bit NQ of VBOC_ACL_FUSED_NQ): the triple only - the fusion makes the
   // triple's data-generation launch 2.4 % faster (profiles/r04_bytes_ab.json) but the double's 10k launches 4.3 %
   // (dg loop) / 10.2 % (first solves) slower (profiles/r05_double_acl_ab.json).
-#ifndef VBOC_ACL_FUSED_NQ
-#define VBOC_ACL_FUSED_NQ (1 << 3)
-#endif
+  // (VBOC_ACL_FUSED_NQ's default, 1 << 3, is set in front of WaveLayout)
   static constexpr bool ACL_FUSED = FM && ((VBOC_ACL_FUSED_NQ >> NQ) & 1);
   // factor_mfma's junk target: lanes without an output write the slot's tail past the written-back fields
   static constexpr int FJUNK = L::OX;
@@ -1167,9 +1218,7 @@ struct Coop {
   // (the factorisation -4.9 % cycles, profiles/r05_factor_loop_experiments.json).  A rounding-level change (round 3 /
   // 5 kept it off because a digest or one tolerance decision moved, profiles/r03z_rinv_ab.json); on since round 6
   // under the tolerance parity rule, with PFUSE above.  -DVBOC_RINV=0: the Cholesky form.
-#ifndef VBOC_RINV
-#define VBOC_RINV 1
-#endif
+  // (the default, 1, is set in front of WaveLayout)
   static constexpr bool RINV = VBOC_RINV && FM && NU == 3;
   // VFUSE (bit 16 of VBOC_FUSE): the predictor's vector step inside factor_mfma, see vstep there
   static constexpr bool VFUSE = FAC1 && ACL_FUSED && RINV && (VBOC_FUSE & 16);
@@ -1210,7 +1259,7 @@ struct Coop {
 #define FS5(i) if constexpr (FSPL == 5) { SPROF(i) }
     SPROF_DECL(FSPL)
     const int c = t & 15, g = t >> 4;
-    constexpr int HS = L::XS;   // H_u image [8][16] (rows g and 4 + g of every lane group); XS is free here
+    constexpr int HS = L::HU;   // H_u image [8][16] (rows g and 4 + g of every lane group)
     // initial state: P_N = diag(D_N), Pi = E' (velocity selection), Sc = 0, LINE = 0
     dbl4 Dm;
     UNR for (int r = 0; r < 4; ++r) {
@@ -1291,6 +1340,13 @@ struct Coop {
     // pass; at the end it is 4-5 % faster (profiles/r07_probe_vfuse_ab.jsonl).
     double pcur = 0.0, kfv = 0.0;
     const int kfo = t < NU ? OKF + t : FJUNK;
+    // KLDS: k_f of stage k goes to its staging row, not through the slot into the record (lanes past NU write
+    // their own TRASH word); the slot's k_f words then keep stale values that nothing reads
+    const int kfx = t < NU ? L::XS + L::XKF + t : L::TRASH + t, kfs = t < NU ? XR : 0;
+    auto kf_out = [&](int sl, int k) {
+      if constexpr (KLDS) s[kfx + k * kfs] = kfv;
+      else s[fslot(sl) + kfo] = kfv;
+    };
     if constexpr (VFUSE) pcur = st(N, ODA + (t < NX ? t : NX - 1));
     auto vstep = [&](int sl) {
       const int kb = fslot(sl);
@@ -1328,7 +1384,7 @@ struct Coop {
         vstep((j - 1) % L::NSF);   // the write-back follows at the end of the trip
       } else if constexpr (ACL_FUSED) {
         acl_slot((j - 1) % L::NSF);                   // LDS ops of this wave run in order: the write-back's
-        ring_wb<OK, L::OX>((j - 1) % L::NSF, k + 1);  // reads of the slot see them
+        ring_wb<OK, L::HOT>((j - 1) % L::NSF, k + 1);  // reads of the slot see them
       } else {
         ring_wb<OK, OC>((j - 1) % L::NSF, k + 1);
       }
@@ -1437,8 +1493,8 @@ struct Coop {
         // stage k + 1: its k_f into its slot, then the slot's outputs to the record (the slot is refilled by the
         // DMA of the next trip at the earliest)
         if (j >= 1) {
-          s[fslot((j - 1) % L::NSF) + kfo] = kfv;
-          ring_wb<OK, L::OX>((j - 1) % L::NSF, k + 1);
+          kf_out((j - 1) % L::NSF, k + 1);
+          ring_wb<OK, L::HOT>((j - 1) % L::NSF, k + 1);
         }
       }
       lsync();
@@ -1460,11 +1516,11 @@ struct Coop {
         if constexpr (VFUSE) {
           acl_slot((j - 1) % L::NSF);
           vstep((j - 1) % L::NSF);
-          s[fslot((j - 1) % L::NSF) + kfo] = kfv;
-          ring_wb<OK, L::OX>((j - 1) % L::NSF, 1);
+          kf_out((j - 1) % L::NSF, 1);
+          ring_wb<OK, L::HOT>((j - 1) % L::NSF, 1);
         } else if constexpr (ACL_FUSED) {
           acl_slot((j - 1) % L::NSF);
-          ring_wb<OK, L::OX>((j - 1) % L::NSF, 1);
+          ring_wb<OK, L::HOT>((j - 1) % L::NSF, 1);
         } else {
           ring_wb<OK, OC>((j - 1) % L::NSF, 1);
         }
@@ -1531,7 +1587,6 @@ struct Coop {
     ldr<OK, NKK>(k, kk);
     ldr<OACL, NX * NX / 2>(k, ac);
     ldr<OPE, NX / 2>(k, pe);
-    gdbl2* dst = (gdbl2*)(g + (long long)k * REC + OC);
     double cv[NX];
     UNR for (int i = 0; i < NX; ++i) {
       double c = gv[i];
@@ -1539,6 +1594,12 @@ struct Coop {
       UNR for (int q = 0; q < NX; ++q) c += ac[q * NX + i] * pe[q];
       cv[i] = c;
     }
+    if constexpr (CLDS) {
+      // staging row k: read by step k of the corrector's vector sweep, which then stores v_k over it
+      UNR for (int i = 0; i < NX; ++i) s[L::XS + k * XR + i] = cv[i];
+      return;
+    }
+    gdbl2* dst = (gdbl2*)(g + (long long)k * REC + OC);
     UNR for (int i = 0; i < NX; i += 2) {
       dbl2 vv;
       vv.x = cv[i];
@@ -1546,7 +1607,7 @@ struct Coop {
       dst[i / 2] = vv;
     }
   }
-  // PRE == false: the constants c' are already in OC (CCORR: prep_corr formed them)
+  // PRE == false: the constants c' are already in OC (CCORR: prep_corr formed them; CLDS: in the staging rows)
   // SWEPT (VFUSE, the predictor): factor_mfma has run the recursion - k_f of stages 1..N-1 is in the records and
   // p_1 in PV; what remains is lin = sum Y'k_f (each lane its stages in the same order, then the same wsum) and
   // stage 0
@@ -1556,6 +1617,7 @@ struct Coop {
     // p_k = c'_k + A_cl,k' p_{k+1},  c'_k = g_x + K'g_u + A_cl' PE_k  (lane i: row i of p);
     // v_k = PE_k + p_{k+1} is kept for k_f.  c' is formed stage-parallel first (-> OC).
     SPROF_DECL(2)
+    static_assert(!CLDS || (L::S_VEC > 1 && L::S_FWD > 1 && (SWEPT || !PRE)), "CLDS: grouped sweeps, constants by prep_corr");
     if constexpr (PRE && !SWEPT) {
       constexpr int NKK = (NU * NX) / 2;
       for (int k = 1 + t; k < N; k += 64) {
@@ -1592,7 +1654,8 @@ struct Coop {
     __syncthreads();
     if constexpr (L::S_VEC > 1) {
       // grouped sweep: group G = stages [1 + G S, 1 + G S + S), walked from the top group down (sweep index
-      // j = ng - 1 - G selects the ring slot); one DMA lands a group's windows [PE | C | ACL], DV groups ahead
+      // j = ng - 1 - G selects the ring slot); one DMA lands a group's windows [PE | C | ACL] (CLDS: [PE | ACL], three
+      // stages instead of two), DV groups ahead
       constexpr int S = L::S_VEC, W = L::W_VEC;
       const int ng = (cnt + S - 1) / S;
       const unsigned voff = grp_off<L::LO_VEC, W, S>();
@@ -1602,7 +1665,7 @@ struct Coop {
       };
       const int i = t < NX ? t : NX - 1;
       // v rows land in XS (lanes past NX write their own TRASH word: no exec-masked store in the chain)
-      const int xm = t < NX ? NX : 0, xb = t < NX ? L::XS + t : L::TRASH + t;
+      const int xm = t < NX ? XR : 0, xb = t < NX ? L::XS + t : L::TRASH + t;
       double pv[NX];
       UNR for (int q = 0; q < NX; ++q) pv[q] = rdlane(pcur, q);
       settle();
@@ -1617,7 +1680,10 @@ struct Coop {
         const int kb = vslot(j & (L::NSV - 1));
         UNR for (int u = 0; u < S; ++u) {
           UNR for (int q = 0; q < NX; ++q) acl[u][q] = s[kb + u * W + (OACL - OPE) + q * NX + i];
-          cc[u] = s[kb + u * W + (OC - OPE) + i];
+          // CLDS: c'_k from staging row k (prep_corr), read for the whole group before its steps store v over the
+          // rows; the top group's rows past stage N - 1 are loaded (the rows' slack) but never used
+          if constexpr (CLDS) cc[u] = s[L::XS + (1 + G * S + u) * XR + i];
+          else cc[u] = s[kb + u * W + (OC - OPE) + i];
           pe[u] = s[kb + u * W + i];
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1667,7 +1733,7 @@ struct Coop {
       double p0 = cc, p1 = 0.0;
       UNR for (int q = 0; q < NX; q += 2) p0 += acl[q] * pv[q];
       UNR for (int q = 1; q < NX; q += 2) p1 += acl[q] * pv[q];
-      if (t < NX) s[L::XS + k * NX + t] = pe + pcur;
+      if (t < NX) s[L::XS + k * XR + t] = pe + pcur;
       pcur = p0 + p1;
       UNR for (int q = 0; q < NX; ++q) pv[q] = rdlane(pcur, q);
       UNR for (int q = 0; q < NX; ++q) acl[q] = an[q];
@@ -1688,7 +1754,11 @@ struct Coop {
       constexpr int F0_ = OKF & ~1, NF = (OKF + NU - F0_ + 1) / 2, Y0_ = OY & ~1, NY = (OPE - Y0_ + 1) / 2;
       for (int k = 1 + t; k < N; k += 64) {
         double kf[2 * NF], yy[2 * NY];
-        ldr<F0_, NF>(k, kf);
+        if constexpr (KLDS) {
+          UNR for (int a = 0; a < NU; ++a) kf[(OKF - F0_) + a] = kfr(k, a);   // vstep's, from the staging row
+        } else {
+          ldr<F0_, NF>(k, kf);
+        }
         ldr<Y0_, NY>(k, yy);
         __builtin_amdgcn_sched_barrier(0);
         UNR for (int j = 0; j < NQ; ++j)
@@ -1706,7 +1776,7 @@ struct Coop {
       double r[NU], Lm[NU * NU];
       UNR for (int a = 0; a < NU; ++a) {
         double x = gg.v[gg.OFF + a];
-        UNR for (int i = 0; i < NX; ++i) x += bb[i * NU + a] * s[L::XS + k * NX + i];
+        UNR for (int i = 0; i < NX; ++i) x += bb[i * NU + a] * s[L::XS + k * XR + i];
         r[a] = x;
       }
       UNR for (int e = 0; e < NU * NU; ++e) Lm[e] = ly[LR_ + e];
@@ -1722,7 +1792,8 @@ struct Coop {
       }
       UNR for (int a = 0; a < NU; ++a) {
         r[a] = -r[a];
-        st(k, OKF + a) = r[a];
+        if constexpr (KLDS) kfr(k, a) = r[a];
+        else st(k, OKF + a) = r[a];
       }
       UNR for (int j = 0; j < NQ; ++j)
         UNR for (int a = 0; a < NU; ++a) lin[j] += ly[Y_ + a * NQ + j] * r[a];
@@ -1786,7 +1857,7 @@ struct Coop {
       if (t < NX) {
         double x = rs * st(0, OE + t);
         UNR for (int a = 0; a < M0; ++a) x += s[L::F0 + t * M0 + a] * w0[a];
-        s[L::XS + NX + t] = x;
+        s[L::XS + XR + t] = x;
         s[L::DXV + t] = x;
       }
     }
@@ -1794,23 +1865,27 @@ struct Coop {
     // dx_{k+1} = c_k + A_cl,k dx_k,  c_k = rs e_k + B_k (k_f - M_k nu)  (lane i: row i); c is formed
     // stage-parallel first (-> OC)
     {
-      constexpr int NBB = (NX * NU + 1) / 2, NFM = (OM + NU * NQ - OKF + 1) / 2;   // B; k_f .. the end of M
+      // B; k_f .. the end of M (KLDS: k_f comes from the staging row, the load is M's 16-B cover)
+      constexpr int NBB = (NX * NU + 1) / 2, FB = KLDS ? (OM & ~1) : OKF, NFM = (OM + NU * NQ - FB + 1) / 2;
       for (int k = 1 + t; k < N; k += 64) {
         double e[NX], bb[2 * NBB], fm[2 * NFM];
         ldr<OE, NX / 2>(k, e);
         ldr<OB, NBB>(k, bb);
-        ldr<OKF, NFM>(k, fm);
+        ldr<FB, NFM>(k, fm);
+        double kf0[NU];
+        UNR for (int a = 0; a < NU; ++a) kf0[a] = KLDS ? kfr(k, a) : 0.0;
         __builtin_amdgcn_sched_barrier(0);
         double kfm[NU];
         UNR for (int a = 0; a < NU; ++a) {
-          double x = fm[a];
-          UNR for (int j = 0; j < NQ; ++j) x -= fm[(OM - OKF) + a * NQ + j] * nun[j];
+          double x = KLDS ? kf0[a] : fm[a];
+          UNR for (int j = 0; j < NQ; ++j) x -= fm[(OM - FB) + a * NQ + j] * nun[j];
           kfm[a] = x;
         }
-        if constexpr (KFM) {
+        if constexpr (KLDS) {
+          UNR for (int a = 0; a < NU; ++a) kfr(k, a) = kfm[a];   // k_f - M nu over k_f, as KFM does in the record
+        } else if constexpr (KFM) {
           UNR for (int a = 0; a < NU; ++a) st(k, OKF + a) = kfm[a];   // read by the step-length pass below
         }
-        gdbl2* dst = (gdbl2*)(g + (long long)k * REC + OC);
         UNR for (int i = 0; i < NX; i += 2) {
           double v[2];
           UNR for (int h2 = 0; h2 < 2; ++h2) {
@@ -1818,10 +1893,17 @@ struct Coop {
             UNR for (int a = 0; a < NU; ++a) c += bb[(i + h2) * NU + a] * kfm[a];
             v[h2] = c;
           }
-          dbl2 vv;
-          vv.x = v[0];
-          vv.y = v[1];
-          dst[i / 2] = vv;
+          if constexpr (CLDS) {
+            // staging row k + 1: read by step k of the recursion, which then stores dx_{k+1} over it
+            s[L::XS + (k + 1) * XR + i] = v[0];
+            s[L::XS + (k + 1) * XR + i + 1] = v[1];
+          } else {
+            gdbl2* dst = (gdbl2*)(g + (long long)k * REC + OC);
+            dbl2 vv;
+            vv.x = v[0];
+            vv.y = v[1];
+            dst[i / 2] = vv;
+          }
         }
       }
       __syncthreads();
@@ -1830,7 +1912,7 @@ struct Coop {
     const int cnt = N - 1;   // stages 1 .. N-1
     __syncthreads();
     if constexpr (L::S_FWD > 1) {
-      // grouped sweep (see vec): group j = stages [1 + j S, 1 + j S + S), windows [C | ACL]
+      // grouped sweep (see vec): group j = stages [1 + j S, 1 + j S + S), windows [C | ACL] (CLDS: [ACL])
       constexpr int S = L::S_FWD, W = L::W_FWD;
       const int ng = (cnt + S - 1) / S;
       const unsigned voff = grp_off<L::LO_FWD, W, S>();
@@ -1839,7 +1921,7 @@ struct Coop {
         dma_s(g + (long long)(1 + G * S) * REC, voff, vslot(j & (L::NSV - 1)));
       };
       const int i = t < NX ? t : NX - 1;
-      const int xm = t < NX ? NX : 0, xb = t < NX ? L::XS + NX + t : L::TRASH + t;
+      const int xm = t < NX ? XR : 0, xb = t < NX ? L::XS + XR + t : L::TRASH + t;
       double dx[NX];
       UNR for (int q = 0; q < NX; ++q) dx[q] = s[L::DXV + q];
       settle();
@@ -1852,8 +1934,11 @@ struct Coop {
         vmwait<L::DV>();   // group j has landed
         const int kb = vslot(j & (L::NSV - 1));
         UNR for (int u = 0; u < S; ++u) {
-          UNR for (int q = 0; q < NX; ++q) acl[u][q] = s[kb + u * W + (OACL - OC) + i * NX + q];
-          cc[u] = s[kb + u * W + i];
+          UNR for (int q = 0; q < NX; ++q) acl[u][q] = s[kb + u * W + (OACL - L::LO_FWD) + i * NX + q];
+          // CLDS: c_k from staging row k + 1 (the constant pass), read for the whole group before its steps store
+          // dx over the rows; rows past stage N - 1 in the top group are loaded (the rows' slack) but never used
+          if constexpr (CLDS) cc[u] = s[L::XS + (2 + j * S + u) * XR + i];
+          else cc[u] = s[kb + u * W + i];
         }
         __builtin_amdgcn_sched_barrier(0);
         UNR for (int u = 0; u < S; ++u) {
@@ -1902,7 +1987,7 @@ struct Coop {
         UNR for (int q = 0; q < NX; q += 2) p0 += acl[q] * dx[q];
         UNR for (int q = 1; q < NX; q += 2) p1 += acl[q] * dx[q];
         const double dn = p0 + p1;
-        if (t < NX) s[L::XS + (k + 1) * NX + t] = dn;
+        if (t < NX) s[L::XS + (k + 1) * XR + t] = dn;
         UNR for (int q = 0; q < NX; ++q) dx[q] = rdlane(dn, q);
         UNR for (int q = 0; q < NX; ++q) acl[q] = an[q];
         cc = cn;
@@ -1915,8 +2000,9 @@ struct Coop {
     // controls of the middle stages, then the step-length tests (stage-parallel)
     typename Lane<NQ>::MinRatio mr{1.0, CORR ? o.tau : 1.0};
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    // K, k_f, chol(Ru), M: the range [OK, OY); KFM: K and k_f - M nu, the range [OK, OKF + NU)
-    constexpr int NKM = KFM ? (OKF + NU - OK + 1) / 2 : (OY - OK + 1) / 2;
+    // K, k_f, chol(Ru), M: the range [OK, OY); KFM: K and k_f - M nu, the range [OK, OKF + NU); KLDS: K alone,
+    // k_f - M nu comes from the staging row
+    constexpr int NKM = KLDS ? (OKF - OK + 1) / 2 : KFM ? (OKF + NU - OK + 1) / 2 : (OY - OK + 1) / 2;
     for (int k = t; k <= N; k += 64) {
       IP r;
       double km[2 * NKM];
@@ -1932,11 +2018,12 @@ struct Coop {
       if (k == 0) {
         UNR for (int i = 0; i < NZ; ++i) d[i] = rec[OT + i];   // written by lane 0 before the sweep
       } else {
-        UNR for (int i = 0; i < NX; ++i) d[i] = s[L::XS + k * NX + i];
+        UNR for (int i = 0; i < NX; ++i) d[i] = s[L::XS + k * XR + i];
         UNR for (int a = 0; a < NU; ++a) {
           double x = 0.0;
           if (k < N) {
-            x = km[OKF - OK + a];
+            if constexpr (KLDS) x = kfr(k, a);
+            else x = km[OKF - OK + a];
             if constexpr (!KFM) {
               UNR for (int j = 0; j < NQ; ++j) x -= km[OM - OK + a * NQ + j] * nun[j];
             }
@@ -2058,7 +2145,7 @@ struct Coop {
       const double dz = st(N, ODZ + i);
       const double lam = o.lm * dz - st(N, OQL + i) + st(N, OQU + i) +
                          (i >= NQ ? par(PF::QNU + (i >= NQ ? i - NQ : 0)) : 0.0);
-      s[L::XS + (N - 1) * NX + i] = lam;
+      s[L::XS + (N - 1) * XR + i] = lam;
       s[L::DXV + i] = lam;
       fin = isfinite(dz);
     }
@@ -2099,7 +2186,7 @@ struct Coop {
       const double x = p0 + p1;
       if (t < NX) {
         s[wb + t] = x;
-        s[L::XS + (k - 1) * NX + t] = x;
+        s[L::XS + (k - 1) * XR + t] = x;
       }
       UNR for (int q = 0; q < NX; ++q) ac[q] = an[q];
       cc = cn;
@@ -2107,7 +2194,7 @@ struct Coop {
     }
     __syncthreads();   // drains the clamped tail DMAs before the ring is reused
     for (int k = t; k < N; k += 64) {
-      UNR for (int i = 0; i < NX; ++i) st(k, ODA + i) = s[L::XS + k * NX + i];
+      UNR for (int i = 0; i < NX; ++i) st(k, ODA + i) = s[L::XS + k * XR + i];
     }
     __syncthreads();
     return fin;
@@ -2359,7 +2446,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WavesPerEu<N
 void k_wave(Work w, Opts o, Inputs in, SlotState ss, WaveJobs jb) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int t = (int)threadIdx.x;
-  Coop<NQ, FM, HC> C(smem, gptr(jb.regions) + (long long)blockIdx.x * jb.region_doubles, w, o, t);
+  // LV = 0: this kernel keeps round 7's passes and record order for every instantiation (the code-object layout
+  // note at its end: with the LDS-vector passes k_wave<3, true> outgrows its alignment step by more than the s_nop
+  // block can give back); the data-generation kernels k_dg / k_ts run them
+  Coop<NQ, FM, HC, 0> C(smem, gptr(jb.regions) + (long long)blockIdx.x * jb.region_doubles, w, o, t);
   if constexpr (HC) C.gh = gptr(jb.hc) + (long long)blockIdx.x * jb.hc_doubles;
   for (;;) {
     unsigned idx = 0;
@@ -2422,7 +2512,7 @@ void k_wave(Work w, Opts o, Inputs in, SlotState ss, WaveJobs jb) {
   // 96 s_nop (384 bytes), run once by a workgroup that has found the job queue empty, put the kernel's end back
   // into the same alignment step, so every arm kernel keeps the bytes the GPU suite validated.  To be dropped when
   // the arm's digests are next re-recorded after a GPU run of tests/test_ur5.py.
-  if constexpr (NQ == 3 && FM && !HC && Coop<NQ, FM, HC>::VFUSE) asm volatile(".rept 96\n\ts_nop 0\n\t.endr");
+  if constexpr (NQ == 3 && FM && !HC && Coop<NQ, FM, HC, 0>::VFUSE) asm volatile(".rept 96\n\ts_nop 0\n\t.endr");
 }
 
 // compact the slots still iterating (phase 1 at a round boundary) into list[]

@@ -1495,7 +1495,8 @@ struct vboc_solver {
   double* regions = nullptr;
   long long n_regions = 0, region_doubles = 0, group_cap = 0;
   double mall_mib = 256.0;          // MALL budget for the resident problems' hot stage fields (0: off)
-  size_t wave_lds = 0;
+  size_t wave_lds = 0;              // dynamic LDS of the wave kernels (WaveLayout<nq>)
+  size_t wave_lds_lv = 0;           // ... of the kernels whose layout keeps per-stage vectors in LDS rows (lds_vec_mask)
   bool coop_ok = false;
   long long coop_count = 0;
   // free-time solver (ft.h): one problem per wave, per-workgroup stage-record regions
@@ -1661,9 +1662,14 @@ static int launch_ft(vboc_solver* h, const Inputs& in, hipStream_t st, const Mpc
 // is sized to stay inside the 256 MiB MALL (Infinity Cache) of MI355X - measured on the 100k triple
 // batch (profiles/r01_wave_groups_sweep.log): 1024 groups 5434, 1408 groups 6212, 2048 groups 5504
 // solves/s.  `wave_groups` overrides; `mall_mib` changes the budget.
-static long long wave_group_budget(const vboc_solver* h, int nmax) {
-  const long long hot = (long long)(h->nq == 1 ? WaveLayout<1>::OX
-                                    : (h->nq == 2 ? WaveLayout<2>::OX : (h->nq == 3 ? WaveLayout<3>::OX : WaveLayout<4>::OX))) *
+// dg: a launch of the data-generation kernels k_dg / k_ts.  The triple's MFMA instantiations of those keep the
+// sweeps' per-stage vectors in LDS and a shorter hot stream (coop.h, lds_vec_mask; k_wave<3, true> does not).
+static long long wave_group_budget(const vboc_solver* h, int nmax, bool dg) {
+  const bool lv = dg && h->nq == 3 && h->factor_mfma;
+  const long long hot = (long long)(h->nq == 1 ? WaveLayout<1>::HOT
+                                    : (h->nq == 2 ? WaveLayout<2>::HOT
+                                       : (h->nq == 3 ? (lv ? WaveLayout<3, lds_vec_mask(3, true, false)>::HOT : WaveLayout<3>::HOT)
+                                                     : WaveLayout<4>::HOT))) *
                         (long long)(nmax + 1) * (long long)sizeof(double);
   const long long g = (long long)(0.92 * h->mall_mib * 1024.0 * 1024.0) / (hot > 0 ? hot : 1);
   return g < 256 ? 256 : g;
@@ -1672,7 +1678,7 @@ static long long wave_group_budget(const vboc_solver* h, int nmax) {
 static hipError_t launch_wave(vboc_solver* h, const WaveJobs& jb, long long jobs, hipStream_t st, const Work& w,
                               const Inputs& in, const SlotState& ss) {
   long long groups = jobs < h->n_regions ? jobs : h->n_regions;
-  const long long cap = h->group_cap > 0 ? h->group_cap : (h->mall_mib > 0 ? wave_group_budget(h, in.nmax) : 0);
+  const long long cap = h->group_cap > 0 ? h->group_cap : (h->mall_mib > 0 ? wave_group_budget(h, in.nmax, false) : 0);
   if (cap > 0 && groups > cap) groups = cap;
   if (groups < 1) return hipSuccess;
   h->last_groups = groups;
@@ -1702,8 +1708,9 @@ static hipError_t launch_dg(vboc_solver* h, const DgJobs& J, const Inputs& in, l
                            bool testing = false) {
   const void* fn = testing ? (const void*)k_ts<NQ, FM> : (const void*)k_dg<NQ, FM>;
   bool& attr = h->dg_attr[(FM ? 1 : 0) + (testing ? 2 : 0)];
+  const size_t lds = lds_vec_mask(NQ, FM, false) ? h->wave_lds_lv : h->wave_lds;   // this instantiation's layout
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->wave_lds);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     attr = true;
   }
@@ -1713,10 +1720,10 @@ static hipError_t launch_dg(vboc_solver* h, const DgJobs& J, const Inputs& in, l
   if (e == hipSuccess) e = hipStreamSynchronize(st);   // J and in live on the host stack
   if (e != hipSuccess) return e;
   if (testing)
-    hipLaunchKernelGGL((k_ts<NQ, FM>), dim3((unsigned)groups), dim3(64), h->wave_lds, st, h->w, h->o, in,
+    hipLaunchKernelGGL((k_ts<NQ, FM>), dim3((unsigned)groups), dim3(64), lds, st, h->w, h->o, in,
                        (const Inputs*)h->dg_in, (const DgJobs*)h->dg_jobs, jb);
   else
-    hipLaunchKernelGGL((k_dg<NQ, FM>), dim3((unsigned)groups), dim3(64), h->wave_lds, st, h->w, h->o, in,
+    hipLaunchKernelGGL((k_dg<NQ, FM>), dim3((unsigned)groups), dim3(64), lds, st, h->w, h->o, in,
                        (const Inputs*)h->dg_in, (const DgJobs*)h->dg_jobs, jb);
   return hipGetLastError();
 }
@@ -1797,6 +1804,8 @@ int vboc_create(int nq, int nmax, int slots, int device, vboc_handle* out) {
     h->wave_lds = nq == 1 ? WaveLayout<1>::lds_bytes(nmax)
                           : (nq == 2 ? WaveLayout<2>::lds_bytes(nmax)
                                      : (nq == 3 ? WaveLayout<3>::lds_bytes(nmax) : WaveLayout<4>::lds_bytes(nmax)));
+    // k_dg / k_ts<3, true> carry more LDS rows (launch_dg); the occupancy and the regions below are k_wave's
+    h->wave_lds_lv = nq == 3 ? WaveLayout<3, lds_vec_mask(3, true, false)>::lds_bytes(nmax) : h->wave_lds;
     h->region_doubles = nq == 1 ? (long long)WaveLayout<1>::region_doubles(nmax)
                                 : (nq == 2 ? (long long)WaveLayout<2>::region_doubles(nmax)
                                            : (nq == 3 ? (long long)WaveLayout<3>::region_doubles(nmax)
@@ -1812,7 +1821,7 @@ int vboc_create(int nq, int nmax, int slots, int device, vboc_handle* out) {
     if (cus < 1) cus = 256;
     h->n_regions = (long long)per_cu * cus;
     if (h->n_regions > 16384) h->n_regions = 16384;
-    if (h->wave_lds > 160 * 1024) h->n_regions = 0;
+    if (h->wave_lds > 160 * 1024 || h->wave_lds_lv > 160 * 1024) h->n_regions = 0;
     h->coop_ok = h->n_regions > 0 &&
                  hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->wave_lds) == hipSuccess &&
                  hipMalloc((void**)&h->regions, sizeof(double) * (size_t)h->region_doubles * (size_t)h->n_regions) ==
@@ -2472,7 +2481,7 @@ static int dg_prepare(vboc_handle h, vboc_dg_batch_t* b, int* done_flag, const i
   long long groups = b->B < h->n_regions ? b->B : h->n_regions;
   // resident problems: their hot stage records at the horizons data generation uses (N_start .. +12) fit the MALL
   const long long cap = h->group_cap > 0 ? h->group_cap
-                                         : (h->mall_mib > 0 ? wave_group_budget(h, b->N_start + 10) : 0);
+                                         : (h->mall_mib > 0 ? wave_group_budget(h, b->N_start + 10, true) : 0);
   if (cap > 0 && groups > cap) groups = cap;
   h->last_groups = groups;
   // per-workgroup arrays: the solver's one-problem batch (Inputs layout) + x_sol, u_sol, saved rows, state
@@ -2638,7 +2647,7 @@ int vboc_testing_test(vboc_handle h, vboc_tt_batch_t* b, void* stream) {
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   long long groups = b->B < h->n_regions ? b->B : h->n_regions;
-  const long long cap = h->group_cap > 0 ? h->group_cap : (h->mall_mib > 0 ? wave_group_budget(h, b->N_start + 10) : 0);
+  const long long cap = h->group_cap > 0 ? h->group_cap : (h->mall_mib > 0 ? wave_group_budget(h, b->N_start + 10, false) : 0);
   if (cap > 0 && groups > cap) groups = cap;
   h->last_groups = groups;
   const int nq = h->nq, NXR = 2 * nq + 1, NU = nq, NP = nq + 1, nm = h->nmax;
