@@ -289,8 +289,12 @@ int vboc_hjr_solve_batch(vboc_handle h, const vboc_hjr_batch_t* batch, void* str
  * times cost_scale) + 1/2 |x_N - yref_e|^2_We, Gauss-Newton Hessian; x_0 fixed; path boxes lbx/ubx, lbu/ubu,
  * terminal box lbx_e/ubx_e; row lh <= NN(x_N) - max(|x_N[2:]|, 1e-3) <= uh with NeuralNetDIR(2nq, hidden, 1)
  * (hidden 0: no row); rti 1 = SQP_RTI (one QP, the full step; status 0 or 4), 0 = SQP with the handle's options.
- * Device pointers except the OCP's constant vectors W, We, yref, yref_e (host); asynchronous on `stream`.  The
- * handle: nq = 3, nmax >= N.
+ * Device pointers except the OCP's constant vectors W, We, yref, yref_e (host); asynchronous on `stream`.
+ * Chains (the handle's nq, nmax >= N): nq = 3 as above; nq = 2 is OCPdoublependulumINIT.OCP_solve(x0, q_ref,
+ * x_sol_guess, u_sol_guess) of VBOC/Safe MPC/<variant>/doublependulum_class_fixedveldir.py (no_constraints: hidden 0;
+ * hard_terminal_constraints: the terminal row; q_ref through yref_b / yref_e_b below); nq = 1 (the reference has no
+ * Safe-MPC pendulum; the tracking OCP of AL/pendulum_class_al.py) runs with hidden = 0 only, since the row's x[2:] is
+ * empty for one link: hidden > 0 on an nq = 1 handle is VBOC_ERR_UNSUPPORTED.  nq = 4 is VBOC_ERR_UNSUPPORTED.
  *   x0[B][2nq], x_guess[B][N+1][2nq], u_guess[B][N][nq]; lbx..ubx_e [2nq] / [nq], W[3nq], We[2nq], yref[3nq],
  *   yref_e[2nq]; W0[hidden][2nq], b0[hidden], W1[hidden][hidden], b1[hidden], W2[hidden], b2[1] (FP64 copies of
  *   model.parameters()); outputs status[B], x_out[B][N+1][2nq], u_out[B][N][nq], cost[B], sqp_iter[B],
@@ -310,6 +314,11 @@ typedef struct {
   int* sqp_iter;
   int* qp_iter;
   double* h_out;
+  /* per-problem references (device; NULL = the batch's host yref / yref_e, so a zero-initialised struct keeps the
+   * meaning it had before these fields): yref_b[B][3nq], yref_e_b[B][2nq] - the 2dof classes'
+   * OCP_solve(x0, q_ref, x_sol_guess, u_sol_guess), which sets yref / yref_e on every call */
+  const double* yref_b;
+  const double* yref_e_b;
 } vboc_mpc_batch_t;
 int vboc_mpc_solve_batch(vboc_handle h, const vboc_mpc_batch_t* batch, void* stream);
 
@@ -323,7 +332,11 @@ int vboc_mpc_solve_batch(vboc_handle h, const vboc_mpc_batch_t* batch, void* str
  * (soft_traj_constraints/3dof_sym.py:102-105, receiding_hard_constraints/3dof_sym.py:41-46); the upper side
  * (uh = 1e6, zu = Zu = 0) is never active and kept hard.  W_b / We_b: each problem's stage weights, the receding
  * driver's cost_set(i, "W", block_diag(Q, R)) / cost_set(N, "W", Q) (:36-40; NULL: the batch's host W / We).  Device
- * pointers: Zl [B][N+1] (required), zl [B][N+1] (NULL = 0), W_b [B][3nq], We_b [B][2nq].  hidden > 0 required. */
+ * pointers: Zl [B][N+1] (required), zl [B][N+1] (NULL = 0), W_b [B][3nq], We_b [B][2nq].  hidden > 0 required.
+ * Chains: nq = 3 as above; nq = 2 is the soft-row OCPdoublependulumINIT of soft_traj_constraints/,
+ * receiding_hard_constraints/ and parallel/doublependulum_class_fixedveldir.py (parallel/2dof_sym.py's retries over
+ * the placement of one stiff Zl are independent problems of one batch: same x0 and guesses, different Zl rows);
+ * nq = 1 and nq = 4 are VBOC_ERR_UNSUPPORTED (the soft rows need the network, and one link has no x[2:]). */
 typedef struct {
   double safety_margin;
   const double* Zl;
@@ -343,7 +356,11 @@ int vboc_mpc_soft_solve_batch(vboc_handle h, const vboc_mpc_batch_t* batch, cons
  * or 2 (any other status), as compute_problem returns.  LINEAR_LS cost 1/2 |[x; u]|^2_W on stages 0..N-1 (times
  * cost_scale) + 1/2 |x_N|^2_We, yref = 0; path boxes lbx/ubx, lbu/ubu; terminal lbx_e/ubx_e (lb == ub: fixed, the
  * class's zero final velocity).  Device pointers except W [3nq] / We [2nq] (host); asynchronous on `stream`.
- * The handle: nq = 3, nmax >= N.  x0[B][2nq], x_guess (optional, see the struct); outputs label[B], status[B],
+ * Chains (the handle's nq, nmax >= N): nq = 3 as above; nq = 2 is OCPdoublependulumINIT.compute_problem /
+ * compute_problem_nnguess (AL/doublependulum_class_al.py, fanned out by testing / testing_guess of
+ * AL/doublependulum_al.py); nq = 1 is OCPpendulumINIT.compute_problem (AL/pendulum_class_al.py: the damped
+ * pendulum, |F| <= 3; AL/pendulum_al.py); nq = 4 is VBOC_ERR_UNSUPPORTED.
+ * x0[B][2nq], x_guess (optional, see the struct); outputs label[B], status[B],
  * x_out[B][N+1][2nq] (get(i, "x")), u_out[B][N][nq], qp_iter[B]. */
 typedef struct {
   int B, N;

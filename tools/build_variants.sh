@@ -9,7 +9,7 @@ if [ $# -eq 0 ]; then set -- $(for p in 1 2 3 4 5 6 7 8; do echo "rep$p:-DVBOC_R
 pids=()
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
-  hipcc --offload-arch=gfx950 -std=c++17 -fPIC -O3 -shared $flags vboc_amd/csrc/vboc_solver.hip \
+  hipcc --offload-arch=gfx950 -std=c++17 -fPIC -O3 -shared $flags vboc_amd/csrc/vboc_solver.hip vboc_amd/csrc/ft_chains.hip \
         -o vboc_amd/variants/libvboc_amd_$name.so &
   pids+=($!)
   if [ ${#pids[@]} -ge 4 ]; then wait ${pids[0]}; pids=("${pids[@]:1}"); fi

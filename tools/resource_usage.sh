@@ -4,7 +4,7 @@
 # usage: bash tools/resource_usage.sh [extra hipcc flags]   -> prints one line per kernel of interest
 cd "$(dirname "$0")/.."
 hipcc --offload-arch=gfx950 -std=c++17 -fPIC -O3 -shared "$@" -Rpass-analysis=kernel-resource-usage \
-      vboc_amd/csrc/vboc_solver.hip -o /tmp/vboc_resource_probe.so 2> /tmp/vboc_resource.txt
+      vboc_amd/csrc/vboc_solver.hip vboc_amd/csrc/ft_chains.hip -o /tmp/vboc_resource_probe.so 2> /tmp/vboc_resource.txt
 python3 - <<'EOF'
 import re
 cur, rows = None, {}

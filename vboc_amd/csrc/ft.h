@@ -61,6 +61,10 @@ struct FtL {
 // (sm = 100 - safety_margin) on every stage 0..N, soft lower sides with the per-problem per-stage slack weights zl / Zl
 // [B][N + 1] (oracle/vboc_oracle_ft.c header: the slack eliminated per stage); Wb / Web [B][3 nq] / [B][2 nq]: per-problem
 // stage weights (the receding driver's cost_set(i, "W")), nullptr = wq / we
+// Yb / Yeb [B][3 nq] / [B][2 nq]: per-problem references (the 2dof classes' OCP_solve(x0, q_ref, ...), which sets
+// yref / yref_e per call: doublependulum_class_fixedveldir.py), nullptr = yr / yre
+// Chains: NQ 1, 2, 3; the row's x[2:] is empty for one link, so NQ 1 runs with hid == 0 only.  The per-problem references
+// are the YB = true form of the solver (k_ftr<NQ>, instantiated in ft_chains.hip); YB = false is k_ft, unchanged.
 constexpr int FT_NN_MAX = 512;
 struct MpcArgs {
   int on, rti, hid, soft;
@@ -71,10 +75,26 @@ struct MpcArgs {
   const double *zl, *Zl, *Wb, *Web;
   double* hrow;   // [B] h(x_N) of each result (nullptr: not written)
 };
+// k_ftr's arguments: MpcArgs and the per-problem references (k_ft keeps MpcArgs)
+struct MpcArgsY : MpcArgs {
+  const double *Yb, *Yeb;
+};
+template <bool YB>
+struct FtArgs { using type = MpcArgs; };
+template <>
+struct FtArgs<true> { using type = MpcArgsY; };
+
+// this problem's tracking references (MpcArgs yr / yre or Yb / Yeb): state of the YB form only
+template <int NQ, bool YB>
+struct FtRef {
+  double yr[3 * NQ + 1], yre[2 * NQ + 1];
+};
+template <int NQ>
+struct FtRef<NQ, false> {};
 
 // MP: the Safe-MPC instantiation (k_ft<3, true>); the free-time pendulum solver carries no network buffers
-template <int NQ, bool MP>
-struct FtShared {
+template <int NQ, bool MP, bool YB = false>
+struct FtShared : FtRef<NQ, YB> {
   static constexpr int NX = FtL<NQ, MP>::NX, NU = FtL<NQ, MP>::NU, NNB = MP ? FT_NN_MAX : 1;
   int N, nf0, ne, pid, bad;
   int f0[NX], ei[NX], fix[NX];
@@ -193,17 +213,17 @@ __device__ __forceinline__ void ft_chol_solve(const double* L, int m, double* b)
   }
 }
 
-template <int NQ, bool MP = false>
+template <int NQ, bool MP = false, bool YB = false>
 struct Ft {
   using L = FtL<NQ, MP>;
   static constexpr int NX = L::NX, NU = L::NU, NZ = L::NZ, N2 = 2 * NQ;
-  FtShared<NQ, MP>& sh;
+  FtShared<NQ, MP, YB>& sh;
   double* g;     // this workgroup's stage records
   const Opts& o;
   int t;
-  const MpcArgs& mp;
+  const typename FtArgs<YB>::type& mp;
 
-  __device__ Ft(FtShared<NQ, MP>& s_, double* g_, const Opts& o_, int t_, const MpcArgs& mp_)
+  __device__ Ft(FtShared<NQ, MP, YB>& s_, double* g_, const Opts& o_, int t_, const typename FtArgs<YB>::type& mp_)
       : sh(s_), g(g_), o(o_), t(t_), mp(mp_) {}
 
   // ---- Safe-MPC terminal row (all lanes; x uniform): h(x) = NN(z(x)) - vn(x), grad (NX, uniform) if asked ----
@@ -294,14 +314,23 @@ struct Ft {
     if (k == sh.N) return sh.we[i];
     return mp.cs * sh.wq[k == 0 ? (i < sh.nf0 ? sh.f0[i] : NX + (i - sh.nf0)) : i];
   }
+  // this problem's references [x; u] / x_N, laid out like wq / we
+  __device__ __forceinline__ const double* yr() const {
+    if constexpr (YB) return sh.yr;
+    else return mp.yr;
+  }
+  __device__ __forceinline__ const double* yre() const {
+    if constexpr (YB) return sh.yre;
+    else return mp.yre;
+  }
   __device__ __forceinline__ double track(int k, const double* x, const double* u) const {
     double c = 0.0;
     if (k == sh.N) {
-      for (int i = 0; i < NX; ++i) { const double d = x[i] - mp.yre[i]; c += sh.we[i] * d * d; }
+      for (int i = 0; i < NX; ++i) { const double d = x[i] - yre()[i]; c += sh.we[i] * d * d; }
       return 0.5 * c;
     }
-    for (int i = 0; i < NX; ++i) { const double d = x[i] - mp.yr[i]; c += sh.wq[i] * d * d; }
-    for (int a = 0; a < NU; ++a) { const double d = u[a] - mp.yr[NX + a]; c += sh.wq[NX + a] * d * d; }
+    for (int i = 0; i < NX; ++i) { const double d = x[i] - yr()[i]; c += sh.wq[i] * d * d; }
+    for (int a = 0; a < NU; ++a) { const double d = u[a] - yr()[NX + a]; c += sh.wq[NX + a] * d * d; }
     return 0.5 * mp.cs * c;
   }
   // ---- the Safe-MPC rows (oracle/vboc_oracle_ft.c frow_*: the same expressions) ----------------------------
@@ -392,9 +421,9 @@ struct Ft {
     if (MP) {   // W ([x; u] - yref) at the current iterate
       double v, lb, ub;
       (void)comp(k, i, v, lb, ub);
-      if (k == sh.N) return sh.we[i] * (v - mp.yre[i]);
+      if (k == sh.N) return sh.we[i] * (v - yre()[i]);
       const int w = k == 0 ? (i < sh.nf0 ? sh.f0[i] : NX + (i - sh.nf0)) : i;
-      return mp.cs * sh.wq[w] * (v - mp.yr[w]);
+      return mp.cs * sh.wq[w] * (v - yr()[w]);
     }
     if (k == 0) return i < sh.nf0 ? sh.c0[sh.f0[i]] : 0.0;
     if (k == sh.N) return 0.0;
@@ -439,6 +468,16 @@ struct Ft {
         }
         if (mp.Web)
           for (int i = 0; i < N2; ++i) sh.we[i] = mp.Web[(long long)pid * N2 + i];
+      }
+      if constexpr (YB) {   // this problem's references, laid out like the weights
+        for (int i = 0; i < NX + NU; ++i) sh.yr[i] = mp.yr[i];
+        for (int i = 0; i < NX; ++i) sh.yre[i] = mp.yre[i];
+        if (mp.Yb) {
+          for (int i = 0; i < N2; ++i) sh.yr[i] = mp.Yb[(long long)pid * (N2 + NU) + i];
+          for (int a = 0; a < NU; ++a) sh.yr[NX + a] = mp.Yb[(long long)pid * (N2 + NU) + N2 + a];
+        }
+        if (mp.Yeb)
+          for (int i = 0; i < N2; ++i) sh.yre[i] = mp.Yeb[(long long)pid * N2 + i];
       }
       sh.bad = bad;
     }
@@ -1255,6 +1294,38 @@ __global__ __launch_bounds__(64) void k_ft(Opts o, Inputs in, double* regions, l
   __shared__ int job;
   const int t = (int)threadIdx.x;
   Ft<NQ, MP> F(sh, regions + (long long)blockIdx.x * region_doubles, o, t, mp);
+  for (;;) {
+    if (t == 0) job = (int)atomicAdd(head, 1u);
+    __syncthreads();
+    const int pid = job;
+    __syncthreads();
+    if (pid >= in.B) break;
+    F.load(in, pid);
+    if (sh.bad) {
+      if (t == 0) {
+        in.status[pid] = 5;
+        in.cost[pid] = NAN;
+        in.sqp_iter[pid] = 0;
+        in.qp_iter[pid] = 0;
+      }
+      __syncthreads();
+      continue;
+    }
+    int it = 0, qit = 0;
+    const int status = F.run(it, qit);
+    F.store(in, status, it, qit);
+    __syncthreads();
+  }
+}
+
+// k_ft for the tracking OCP with per-problem references (the YB form; every pendulum chain)
+template <int NQ>
+__global__ __launch_bounds__(64) void k_ftr(Opts o, Inputs in, double* regions, long long region_doubles,
+                                           unsigned* head, MpcArgsY mp) {
+  __shared__ FtShared<NQ, true, true> sh;
+  __shared__ int job;
+  const int t = (int)threadIdx.x;
+  Ft<NQ, true, true> F(sh, regions + (long long)blockIdx.x * region_doubles, o, t, mp);
   for (;;) {
     if (t == 0) job = (int)atomicAdd(head, 1u);
     __syncthreads();

@@ -32,6 +32,7 @@
 
 #include "../../include/vboc.h"
 #include "model.h"
+#include "solver_types.h"
 
 #define UNR _Pragma("unroll")
 #ifdef VBOC_WAVES
@@ -42,17 +43,6 @@
 
 namespace vboc {
 
-struct Opts {
-  double tol_stat, tol_eq, tol_ineq, tol_comp;
-  double qp_tol_stat, qp_tol_eq, qp_tol_comp;
-  double alpha_min, alpha_red, lm, mu0, push, tau;
-  int max_iter, qp_max_iter;
-  // Cartesian path constraint hlh <= |tip(theta_k) - (hxc, hyc)|^2 <= huh on stages 0..N-1 (hc != 0;
-  // vboc_set_path_constraint, VBOC/Cartesian constraints/doublependulum_class_fixedveldir.py:154-160)
-  int hc;
-  double hxc, hyc, hlh, huh;
-};
-
 // Slot-major workspace.  Field counts per stage are fixed by NQ.
 struct Work {
   double *X, *U, *PI, *LL, *LU, *WPI;        // SQP iterate + NLP multipliers + merit weights
@@ -62,16 +52,6 @@ struct Work {
   double *F0, *LR0, *M0, *Y0, *PE0, *PAR;     // stage-0 specials, problem parameters (per slot)
   double* HC;                                 // path-constraint rows (allocated with the constraint)
   long long S;                                // number of slots (lanes)
-};
-
-struct Inputs {
-  int B, nmax;
-  const int* N;
-  const double *xg, *ug, *p, *lbx, *ubx, *lbu, *ubu, *lbx0, *ubx0, *lbxe, *ubxe;
-  int* status;
-  double *xo, *uo, *cost;
-  int *sqp_iter, *qp_iter;
-  unsigned int* head;   // work-queue head
 };
 
 // per-slot parameter fields
@@ -1631,9 +1611,14 @@ static hipError_t launch_round(vboc_solver* h, dim3 grid, dim3 block, hipStream_
   return hipGetLastError();
 }
 
+namespace vboc {
+int launch_ft_chains(int nq, unsigned groups, hipStream_t st, const Opts& o, const Inputs& in, double* regions,
+                     long long rd, unsigned* head, const MpcArgsY& mp);   // ft_chains.hip
+}
+
 // free-time solver: a persistent grid of one-wave workgroups, each with its own stage-record region
 template <int NQ>
-static int launch_ft(vboc_solver* h, const Inputs& in, hipStream_t st, const MpcArgs& mp = MpcArgs{}) {
+static int launch_ft(vboc_solver* h, const Inputs& in, hipStream_t st, const MpcArgsY& mp = MpcArgsY{}) {
   const long long rd = mp.on ? FtL<NQ, true>::region_doubles(in.nmax) : FtL<NQ, false>::region_doubles(in.nmax);
   long long groups = in.B < 1024 ? in.B : 1024;
   const size_t need = (size_t)groups * (size_t)rd * sizeof(double);
@@ -1645,15 +1630,16 @@ static int launch_ft(vboc_solver* h, const Inputs& in, hipStream_t st, const Mpc
     h->ft_bytes = need;
   }
   if constexpr (NQ == 3) {
-    if (mp.on) {
+    if (mp.on && !mp.Yb && !mp.Yeb) {   // the triple without per-problem references: the kernel it always ran on
       hipLaunchKernelGGL((k_ft<NQ, true>), dim3((unsigned)groups), dim3(64), 0, st, h->o, in, h->ft_regions, rd, h->head,
-                         mp);
+                         static_cast<const MpcArgs&>(mp));
       return hipGetLastError() == hipSuccess ? 0 : -2;
     }
   }
-  if (mp.on) return -2;   // the Safe-MPC OCP is the triple's
+  // the smaller chains, and the triple with per-problem references: k_ftr<NQ>, in ft_chains.hip
+  if (mp.on) return launch_ft_chains(NQ, (unsigned)groups, st, h->o, in, h->ft_regions, rd, h->head, mp);
   hipLaunchKernelGGL((k_ft<NQ, false>), dim3((unsigned)groups), dim3(64), 0, st, h->o, in, h->ft_regions, rd, h->head,
-                     mp);
+                     static_cast<const MpcArgs&>(mp));
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2317,10 +2303,11 @@ int vboc_al_solve_batch(vboc_handle h, const vboc_al_batch_t* b, void* stream) {
                         b->status, b->x_out, b->u_out, b->qp_iter};
   for (const void* q : ptrs)
     if (!q) return fail(VBOC_ERR_ARG, W + ": NULL array in batch");
-  if (h->nq != 3) return fail(VBOC_ERR_UNSUPPORTED, W + ": the AL labelling OCP is the triple pendulum's (nq = 3)");
+  if (h->nq < 1 || h->nq > 3)
+    return fail(VBOC_ERR_UNSUPPORTED, W + ": the AL labelling OCP is the pendulum chains' (nq = 1, 2, 3)");
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  constexpr int NQ = 3;
+  const size_t NQ = (size_t)h->nq;
   const size_t B = (size_t)b->B, N = (size_t)b->N;
   // the guesses, the cost and the sqp counter the Safe-MPC call writes, in a buffer of their own (mpc_solve owns
   // mpc_buf)
@@ -2336,9 +2323,9 @@ int vboc_al_solve_batch(vboc_handle h, const vboc_al_batch_t* b, void* stream) {
   double* ug = xg + B * (N + 1) * 2 * NQ;
   double* cost = ug + B * N * NQ;
   int* sqp = (int*)(cost + B);
-  hipLaunchKernelGGL(k_al_guess, dim3(256), dim3(256), 0, st, b->B, b->N, NQ, b->x0, xg, ug);
+  hipLaunchKernelGGL(k_al_guess, dim3(256), dim3(256), 0, st, b->B, b->N, h->nq, b->x0, xg, ug);
   HIPCHK(hipGetLastError());
-  static const double zero[3 * NQ] = {0.0};   // yref = yref_e = 0 (:114-115)
+  static const double zero[9] = {0.0};   // yref = yref_e = 0 (:114-115)
   vboc_mpc_batch_t m{};
   m.B = b->B; m.N = b->N; m.rti = 1; m.hidden = 0; m.h = b->h; m.cost_scale = b->cost_scale;
   m.x0 = b->x0; m.x_guess = b->x_guess ? b->x_guess : xg; m.u_guess = ug;   // u = 0 (reset) in both variants
@@ -2362,11 +2349,12 @@ int vboc_mpc_soft_solve_batch(vboc_handle h, const vboc_mpc_batch_t* b, const vb
   return mpc_solve(h, b, soft, stream, W);
 }
 
-static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_soft_t* sf, void* stream,
-                     const std::string& W, int qcf) {
-  if (busy(h, W.c_str())) return VBOC_ERR_ARG;
-  if (!h || !b) return fail(VBOC_ERR_ARG, W + ": NULL argument");
-  if (h->nq != 3) return fail(VBOC_ERR_UNSUPPORTED, W + ": the Safe-MPC OCP is the triple pendulum's (nq = 3)");
+}  // extern "C": a template has C++ linkage
+
+// the tracking OCP of one batch on the handle's chain (the body of mpc_solve below)
+template <int NQ>
+static int mpc_solve_nq(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_soft_t* sf, void* stream,
+                        const std::string& W, int qcf) {
   if (h->o.hc) return fail(VBOC_ERR_UNSUPPORTED, W + ": no path constraint in the Safe-MPC OCP (clear it first)");
   if (b->B < 0 || b->N < 1 || b->N > h->nmax) return fail(VBOC_ERR_ARG, W + ": needs B >= 0 and 1 <= N <= nmax");
   if (b->hidden < 0 || b->hidden > FT_NN_MAX) return fail(VBOC_ERR_ARG, W + ": hidden must be in [0, 512]");
@@ -2380,7 +2368,7 @@ static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_so
     return fail(VBOC_ERR_ARG, W + ": NULL network parameter");
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  constexpr int NQ = 3, NX = 2 * NQ + 1, NU = NQ;
+  constexpr int NX = 2 * NQ + 1, NU = NQ;
   const size_t B = (size_t)b->B, N = (size_t)b->N, H = (size_t)b->hidden;
   const size_t dbl = B * (N + 1) * NX * 2 + B * NX * 6 + B * NU * 2 + B * (NQ + 1) + H * H;
   const size_t need = dbl * sizeof(double) + B * sizeof(int) + 512;
@@ -2403,7 +2391,7 @@ static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_so
   hipLaunchKernelGGL(k_mpc_prep, dim3(256), dim3(256), 0, st, b->B, b->N, NQ, b->h, b->x0, b->x_guess, b->lbx, b->ubx,
                      b->lbu, b->ubu, b->lbx_e, b->ubx_e, xg7, lbx7, ubx7, lbu_b, ubu_b, lbx0, ubx0, lbxe7, ubxe7, pp,
                      Nb);
-  MpcArgs mp{};
+  MpcArgsY mp{};
   mp.on = 1; mp.rti = b->rti ? 1 : 0; mp.hid = b->hidden; mp.cs = b->cost_scale; mp.qcf = qcf;
   const double *Wh = b->W, *Weh = b->We, *yr = b->yref, *yre = b->yref_e;   // host constants
   for (int i = 0; i < 2 * NQ; ++i) { mp.wq[i] = Wh[i]; mp.yr[i] = yr[i]; mp.we[i] = Weh[i]; mp.yre[i] = yre[i]; }
@@ -2415,6 +2403,7 @@ static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_so
     mp.mean = b->mean; mp.std = b->std; mp.lh = b->lh; mp.uh = b->uh;
   }
   mp.hrow = b->h_out;
+  mp.Yb = b->yref_b; mp.Yeb = b->yref_e_b;   // per-problem references (NULL: yref / yref_e)
   mp.soft = 0; mp.sm = 100.0; mp.zl = mp.Zl = mp.Wb = mp.Web = nullptr;
   if (sf) {   // OCPtriplependulumSoftTraj: the margin-scaled row on every stage, soft lower sides
     mp.soft = 1; mp.sm = 100.0 - sf->safety_margin;
@@ -2436,6 +2425,24 @@ static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_so
   HIPCHK(hipGetLastError());
   h->launches = 1;
   return VBOC_OK;
+}
+
+extern "C" {
+
+static int mpc_solve(vboc_handle h, const vboc_mpc_batch_t* b, const vboc_mpc_soft_t* sf, void* stream,
+                     const std::string& W, int qcf) {
+  if (busy(h, W.c_str())) return VBOC_ERR_ARG;
+  if (!h || !b) return fail(VBOC_ERR_ARG, W + ": NULL argument");
+  if (h->nq < 1 || h->nq > 3)
+    return fail(VBOC_ERR_UNSUPPORTED, W + ": the tracking OCPs are the pendulum chains' (nq = 1, 2, 3)");
+  // the row's velocity norm |x[2:]| is empty for one link (the reference has no Safe-MPC class for the pendulum)
+  if (h->nq == 1 && b->hidden > 0)
+    return fail(VBOC_ERR_UNSUPPORTED, W + ": the network row needs nq >= 2 (x[2:] is empty for nq = 1): hidden must be 0");
+  switch (h->nq) {   // the handle's chain picks the instantiation
+    case 1: return mpc_solve_nq<1>(h, b, sf, stream, W, qcf);
+    case 2: return mpc_solve_nq<2>(h, b, sf, stream, W, qcf);
+    default: return mpc_solve_nq<3>(h, b, sf, stream, W, qcf);
+  }
 }
 
 int vboc_solve_batch_host(vboc_handle h, const vboc_batch_t* b) { return solve_host(h, b, false); }

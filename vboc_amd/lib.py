@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("VBOC_LIB") or os.path.join(HERE, "libvboc_amd.so")
 if os.environ.get("VBOC_LIB") and not os.path.realpath(LIB_PATH).startswith(os.path.realpath(ROOT) + os.sep):
     raise RuntimeError(f"VBOC_LIB={LIB_PATH}: only solver builds inside {ROOT} may replace the product library")
 SRC = os.path.join(HERE, "csrc", "vboc_solver.hip")
+SRC_CHAINS = os.path.join(HERE, "csrc", "ft_chains.hip")   # k_ftr<1|2|3>: a translation unit of their own
 
 EXPORTS = ("vboc_create", "vboc_destroy", "vboc_set_option", "vboc_get_option", "vboc_solve_batch",
            "vboc_solve_batch_host", "vboc_solve_batch_ft", "vboc_solve_batch_ft_host", "vboc_rk4_batch", "vboc_rk4_batch_host",
@@ -80,7 +81,8 @@ class MpcBatch(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("x0", "x_guess", "u_guess", "lbx", "ubx", "lbu", "ubu", "lbx_e", "ubx_e",
                                                "W", "We", "yref", "yref_e", "W0", "b0", "W1", "b1", "W2", "b2")] + \
                [(n, ctypes.c_double) for n in ("mean", "std", "lh", "uh")] + \
-               [(n, ctypes.c_void_p) for n in ("status", "x_out", "u_out", "cost", "sqp_iter", "qp_iter", "h_out")]
+               [(n, ctypes.c_void_p) for n in ("status", "x_out", "u_out", "cost", "sqp_iter", "qp_iter", "h_out",
+                                               "yref_b", "yref_e_b")]
 
 
 class MpcSoft(ctypes.Structure):
@@ -102,10 +104,11 @@ DG_CLOCK_HZ = 100e6
 
 
 def build(verbose=False, extra_flags=(), out=None):
-    """hipcc the solver for gfx950 into vboc_amd/libvboc_amd.so (in-tree, -O3, one translation unit).
+    """hipcc the solver for gfx950 into vboc_amd/libvboc_amd.so (in-tree, -O3; the solver's translation unit first).
     `extra_flags` / `out` build an instrumented variant next to it (e.g. -DVBOC_COOP_PROF)."""
     out = out or LIB_PATH
-    cmd = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-O3", "-shared", *extra_flags, SRC, "-o", out]
+    cmd = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-O3", "-shared", *extra_flags, SRC, SRC_CHAINS, "-o",
+           out]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -384,19 +387,32 @@ class Solver:
         out["_keep"] = W
         return out
 
+    def _check_spec(self, spec, what):
+        """The spec's chain must be the handle's: the shapes below come from spec.nq."""
+        if int(spec.nq) != self.nq:
+            raise VbocError(f"{what}: spec nq = {int(spec.nq)} does not match the solver's handle nq = {self.nq}")
+        return self.nq
+
     def mpc_solve_device(self, spec, x0, x_guess, u_guess, params=None, mean=0.0, std=1.0, rti=False, lh=0.0,
-                         uh=1e6, stream=None, soft=None):
-        """OCPtriplependulumHardTerm.OCP_solve (vboc_mpc_solve_batch, ft.h) for every row of the float64 cuda tensor
-        x0 [B, 6]: guesses [B, N+1, 6] / [B, N, 3] (cuda, float64), spec a safempc.MpcSpec, params the NeuralNetDIR
-        weights as float64 cuda tensors (None: no terminal row).  Returns a dict of device tensors: status, x, u, cost,
-        sqp_iter, qp_iter, h (the row at the result's x_N).
+                         uh=1e6, stream=None, soft=None, yref=None, yref_e=None):
+        """OCPtriplependulumHardTerm.OCP_solve / the 2dof OCPdoublependulumINIT.OCP_solve (vboc_mpc_solve_batch, ft.h)
+        for every row of the float64 cuda tensor x0 [B, 2nq] (nq = spec.nq, the handle's): guesses [B, N+1, 2nq] /
+        [B, N, nq] (cuda, float64), spec a safempc.MpcSpec, params the NeuralNetDIR weights as float64 cuda tensors
+        (None: no terminal row).  Returns a dict of device tensors: status, x, u, cost, sqp_iter, qp_iter, h (the row
+        at the result's x_N).
         soft: OCPtriplependulumSoftTraj (vboc_mpc_soft_solve_batch) - dict(margin=..., Zl=[B, N+1], zl=[B, N+1] or
-        None, W=[B, 9] or None, We=[B, 6] or None), float64 cuda tensors."""
+        None, W=[B, 3nq] or None, We=[B, 2nq] or None), float64 cuda tensors.
+        yref [B, 3nq] / yref_e [B, 2nq] (float64 cuda, optional): per-problem references (the 2dof OCP_solve's q_ref);
+        None: spec.yref / spec.yref_e for every problem."""
         import torch
+        nq = self._check_spec(spec, "mpc_solve_device")
         B, N = x0.shape[0], spec.N
         for t_ in (x0, x_guess, u_guess):
             assert t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()
-        assert tuple(x_guess.shape) == (B, N + 1, 6) and tuple(u_guess.shape) == (B, N, 3)
+        assert tuple(x_guess.shape) == (B, N + 1, 2 * nq) and tuple(u_guess.shape) == (B, N, nq)
+        for t_, w_ in ((yref, 3 * nq), (yref_e, 2 * nq)):
+            assert t_ is None or (t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()
+                                  and tuple(t_.shape) == (B, w_))
         dev = x0.device
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
         bnd = [f64(a) for a in (spec.xmin, spec.xmax, spec.umin, spec.umax, spec.xmin, spec.xmax)]
@@ -416,14 +432,16 @@ class Solver:
                      **{n: w.data_ptr() for n, w in zip(("W0", "b0", "W1", "b1", "W2", "b2"), W)},
                      status=out["status"].data_ptr(), x_out=out["x"].data_ptr(), u_out=out["u"].data_ptr(),
                      cost=out["cost"].data_ptr(), sqp_iter=out["sqp_iter"].data_ptr(),
-                     qp_iter=out["qp_iter"].data_ptr(), h_out=out["h"].data_ptr())
+                     qp_iter=out["qp_iter"].data_ptr(), h_out=out["h"].data_ptr(),
+                     yref_b=yref.data_ptr() if yref is not None else None,
+                     yref_e_b=yref_e.data_ptr() if yref_e is not None else None)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         if soft is None:
             _check(self.lib.vboc_mpc_solve_batch(self.h, ctypes.byref(b), ctypes.c_void_p(st.cuda_stream)))
-            out["_keep"] = (bnd, host, W)
+            out["_keep"] = (bnd, host, W, yref, yref_e)
             return out
         arrs = {}
-        for k_, shp in (("Zl", (B, N + 1)), ("zl", (B, N + 1)), ("W", (B, 9)), ("We", (B, 6))):
+        for k_, shp in (("Zl", (B, N + 1)), ("zl", (B, N + 1)), ("W", (B, 3 * nq)), ("We", (B, 2 * nq))):
             a = soft.get(k_)
             if a is None:
                 continue
@@ -435,26 +453,28 @@ class Solver:
                      We_b=arrs["We"].data_ptr() if "We" in arrs else None)
         _check(self.lib.vboc_mpc_soft_solve_batch(self.h, ctypes.byref(b), ctypes.byref(sf),
                                                   ctypes.c_void_p(st.cuda_stream)))
-        out["_keep"] = (bnd, host, W, arrs)
+        out["_keep"] = (bnd, host, W, arrs, yref, yref_e)
         return out
 
     def al_solve_device(self, spec, x0, x_guess=None, stream=None):
-        """AL's OCPtriplependulumINIT.compute_problem (vboc_al_solve_batch, ft.h) for every row of the float64 cuda
-        tensor x0 [B, 6]; spec a vboc_amd.al.AlSpec; x_guess (float64 cuda [B, N+1, 6], optional):
-        compute_problem_nnguess's stage guesses.  Returns a dict of device tensors: label (1 / 0 / 2), status,
-        x [B, N+1, 6], u [B, N, 3], qp_iter."""
+        """AL's compute_problem of OCPtriplependulumINIT / OCPdoublependulumINIT / OCPpendulumINIT
+        (vboc_al_solve_batch, ft.h) for every row of the float64 cuda tensor x0 [B, 2nq] (nq = spec.nq, the handle's);
+        spec a vboc_amd.al.AlSpec; x_guess (float64 cuda [B, N+1, 2nq], optional): compute_problem_nnguess's stage
+        guesses.  Returns a dict of device tensors: label (1 / 0 / 2), status, x [B, N+1, 2nq], u [B, N, nq],
+        qp_iter."""
         import torch
-        assert x0.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous() and x0.shape[1] == 6
+        nq = self._check_spec(spec, "al_solve_device")
+        assert x0.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous() and x0.shape[1] == 2 * nq
         B, N, dev = x0.shape[0], spec.N, x0.device
         if x_guess is not None:
             assert (x_guess.is_cuda and x_guess.dtype == torch.float64 and x_guess.is_contiguous()
-                    and tuple(x_guess.shape) == (B, N + 1, 6))
+                    and tuple(x_guess.shape) == (B, N + 1, 2 * nq))
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
         bnd = [f64(a) for a in (spec.xmin, spec.xmax, spec.umin, spec.umax, spec.xmin_e, spec.xmax_e)]
         host = [np.ascontiguousarray(a, dtype=np.float64) for a in (spec.W, spec.W_e)]
         out = dict(label=torch.empty(B, dtype=torch.int32, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev),
-                   x=torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev),
-                   u=torch.empty((B, N, 3), dtype=torch.float64, device=dev),
+                   x=torch.empty((B, N + 1, 2 * nq), dtype=torch.float64, device=dev),
+                   u=torch.empty((B, N, nq), dtype=torch.float64, device=dev),
                    qp_iter=torch.empty(B, dtype=torch.int32, device=dev))
         b = AlBatch(B=B, N=N, h=spec.time_step, cost_scale=spec.cost_scale, x0=x0.data_ptr(),
                     x_guess=x_guess.data_ptr() if x_guess is not None else None,
