@@ -122,3 +122,24 @@ def hjr_labels(ocp, Xu_iter, y_pred, q_min=THETA_MIN, q_max=THETA_MAX, v_max=DTH
             else:
                 out[i] = (None, None)
     return out
+
+
+def hjr_labels_arrays(ocp, Xu_iter, y_pred, q_min=THETA_MIN, q_max=THETA_MAX, v_max=DTHETA_MAX, chunk=1 << 18):
+    """hjr_labels as arrays, for candidate sets of millions of rows: (keep [B] bool, label1 [B] uint8).  keep is
+    False where hjr_labels returns (None, None) (an asked candidate whose solve failed); label1 is 1 where its output
+    is [0, 1] (solved with get_cost() < 0) and 0 where it is [1, 0].  The training set of the next fit is
+    Xu_iter[keep] with targets [1 - label1, label1][keep]."""
+    X = np.asarray(Xu_iter, dtype=np.float64)
+    nq = X.shape[1] // 2
+    pos, vel = X[:, :nq], X[:, nq:]
+    inside = np.all((pos >= q_min) & (pos <= q_max), axis=1) & np.all((vel >= -v_max) & (vel <= v_max), axis=1)
+    idx = np.flatnonzero(inside & (np.asarray(y_pred) == 1))
+    keep = np.ones(X.shape[0], dtype=bool)
+    label1 = np.zeros(X.shape[0], dtype=np.uint8)
+    for lo in range(0, idx.size, chunk):          # bounded launches: the problems are independent
+        part = idx[lo:lo + chunk]
+        lab, res = ocp.compute_problems(X[part])
+        solved = np.asarray(lab) == 1
+        keep[part] = solved
+        label1[part] = solved & (np.asarray(res["cost"]) < 0.0)
+    return keep, label1

@@ -274,3 +274,30 @@ def pendulum_free_time_ics(ids, N_range=(20, 60), seed=SEED):
                  ubx0=np.stack([q_init, np.full(B, v_max), np.full(B, 1e-2)], axis=1),
                  lbxe=np.stack([q_fin, np.zeros(B), np.zeros(B)], axis=1),
                  ubxe=np.stack([q_fin, np.zeros(B), np.full(B, 1e-2)], axis=1))
+
+
+# ------------------------------------------------------------------------------------------------
+# candidate sets of the HJR loop (HJR/triplependulum_hjr.py:82-83, :196 and the double / pendulum twins)
+# ------------------------------------------------------------------------------------------------
+HJR_INIT_STREAM, HJR_TEST_STREAM, HJR_ITER_STREAM = 7, 8, 9
+
+
+def hjr_candidates(nq, kind, B, iteration=0, seed=SEED):
+    """np.random.uniform(low, high, size=(B, 2nq)) of the HJR drivers from the Philox streams 7 (kind "init": the
+    state box widened by 10 % of its width on every side, :82), 8 ("test": the state box, :83) and 9 ("iter": the
+    positions in the box, the velocities widened by 20 %, :196; the pendulum keeps the 10 % box of "init",
+    HJR/pendulum_hjr.py:123).  Row r of iteration i (from 1) is id i * B + r of stream 9."""
+    q_min, q_max, v_min, v_max = -np.pi / 4 + np.pi, np.pi / 4 + np.pi, -10.0, 10.0
+    dq, dv = q_max - q_min, v_max - v_min
+    if kind == "init" or (kind == "iter" and nq == 1):
+        lo, hi = [q_min - dq / 10] * nq + [v_min - dv / 10] * nq, [q_max + dq / 10] * nq + [v_max + dv / 10] * nq
+    elif kind == "test":
+        lo, hi = [q_min] * nq + [v_min] * nq, [q_max] * nq + [v_max] * nq
+    elif kind == "iter":
+        lo, hi = [q_min] * nq + [v_min - dv / 5] * nq, [q_max] * nq + [v_max + dv / 5] * nq
+    else:
+        raise ValueError(kind)
+    stream = {"init": HJR_INIT_STREAM, "test": HJR_TEST_STREAM, "iter": HJR_ITER_STREAM}[kind]
+    ids = np.arange(B, dtype=np.uint64) + np.uint64(iteration * B if kind == "iter" else 0)
+    lo, hi = np.array(lo), np.array(hi)
+    return lo + (hi - lo) * uniforms(ids, 2 * nq, seed, stream=stream)

@@ -495,3 +495,238 @@ def make_trainer(nq, device="cpu", native=False, **kw):
     if native and dev.type == "cuda" and fitlib.supported(2 * nq, hidden, k):
         return HipTrainer(nq, device, **kw)
     return DirTrainer(nq, device, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# the HJR / AL classifier (HJR/triplependulum_hjr.py:95-176): BCE fit, classification, RMSE march
+# ------------------------------------------------------------------------------------------------
+CLS_MINIBATCH = {3: 4096, 2: 4096, 1: 64}       # n_minibatch of the three HJR drivers
+CLS_MAX_STEPS = 16384                           # bound of the outward march (the reference has none)
+
+
+def march_reference(classify, X_test, mean, std, max_steps=CLS_MAX_STEPS):
+    """The march of HJR/triplependulum_hjr.py:150-176 restated over all rays at once.  `classify(P)` returns the
+    labels of the float32 rows P [r, 2nq] (raw states; the normalisation (P - mean) / std is the caller's, inside
+    classify).  Every ray accumulates its velocity step by step in float64, as the reference does; one call of
+    classify serves step k of every ray still marching.  Returns (err, steps, flags) as vboc_cls_boundary does."""
+    X = np.asarray(X_test, dtype=np.float64)
+    m, nq = X.shape[0], X.shape[1] // 2
+    vt = X[:, nq:]
+    s2 = vt[:, 0] * vt[:, 0]
+    for j in range(1, nq):
+        s2 = s2 + vt[:, j] * vt[:, j]
+    vel_norm = np.sqrt(s2)
+    label = np.asarray(classify(X.astype(np.float32))).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = np.where(label[:, None] == 1, -1.0, 1.0) * ((1e-2 * vt) / vel_norm[:, None])
+    v = vt.copy()
+    vn = vel_norm.copy()
+    steps = np.zeros(m, dtype=np.int32)
+    capped = np.zeros(m, dtype=bool)
+    act = np.flatnonzero(vel_norm > 1e-2)
+    while act.size:
+        v[act] = v[act] - c[act]
+        steps[act] += 1
+        q2 = v[act, 0] * v[act, 0]
+        for j in range(1, nq):
+            q2 = q2 + v[act, j] * v[act, j]
+        vn[act] = np.sqrt(q2)
+        out = np.asarray(classify(np.c_[X[act, :nq], v[act]].astype(np.float32))).astype(np.int64)
+        go = (out == label[act]) & (vn[act] > 1e-2)
+        cap = go & (steps[act] >= max_steps)
+        capped[act[cap]] = True
+        act = act[go & ~cap]
+    flags = (label | (capped.astype(np.int64) << 1)).astype(np.uint8)
+    return vel_norm - vn, steps, flags
+
+
+class ClsTrainer:
+    """The reference's classifier loop on PyTorch: NeuralNetCLS(2nq, hidden, 2), BCEWithLogitsLoss, Adam(lr), one
+    optimizer for the whole run; fit() is `while val > loss_stop and it < it_max` with val from 1
+    (HJR/triplependulum_hjr.py:95-118).  The CPU path and the comparator of HipClsTrainer.
+
+    fit(F, it_max): F [n, 2nq + 2] float32 = normalised inputs, then the two targets.  The minibatch rows come from
+    `self.sampler(n, 1)`: by default random.sample of a random.Random(seed), or an injected callable (n, steps) ->
+    [steps, k] indices.  predict_labels / boundary_errors run on the device kernels (libvboc_cls.so) when the model
+    is on a GPU and the shape is supported (they are not the NN fit), else on PyTorch."""
+
+    def __init__(self, nq, device="cpu", hidden=100, minibatch=None, lr=1e-3, beta=0.95, stop_val=5e-3, seed=0,
+                 sampler=None, native_eval=True, max_steps=CLS_MAX_STEPS):
+        import random
+        self.nq, self.nin = nq, 2 * nq
+        self.device = torch.device(device)
+        torch.manual_seed(seed)
+        self.hidden = hidden
+        self.model = NeuralNetCLS(self.nin, hidden, 2).to(self.device)
+        self.k = minibatch or CLS_MINIBATCH[nq]
+        self.lr, self.beta, self.stop_val, self.seed = lr, beta, stop_val, seed
+        self.opt = torch.optim.Adam(self.model.parameters(), lr=lr)
+        self.crit = nn.BCEWithLogitsLoss()
+        self._rng = random.Random(seed)
+        self.sampler = sampler or self.sample
+        self.max_steps = max_steps
+        self.total_steps = 0
+        self.last = None
+        self._h = None
+        self._cl = None
+        if native_eval and self.device.type == "cuda":
+            from . import clslib
+            if clslib.supported(self.nin, hidden, self.k):      # a missing library is an error, not a fall-back
+                import ctypes
+                self._cl, self._lib = clslib, clslib.load()
+                h = ctypes.c_void_p()
+                clslib.check(self._lib.vboc_cls_create(self.nin, hidden, self.k, seed, ctypes.byref(h)))
+                self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.vboc_cls_destroy(h)
+            self._h = None
+
+    def sample(self, n, steps=1):
+        """The next `steps` minibatches, [steps, k] row indices: random.sample(range(n), k) each."""
+        return np.array([self._rng.sample(range(n), self.k) for _ in range(steps)], dtype=np.int64)
+
+    def _rows(self, F):
+        return torch.as_tensor(np.asarray(F), dtype=torch.float32).to(self.device).contiguous() \
+            if not torch.is_tensor(F) else F.to(self.device, torch.float32).contiguous()
+
+    def fit(self, F, it_max):
+        F = self._rows(F)
+        n = F.shape[0]
+        if n < self.k:
+            raise ValueError(f"need at least {self.k} rows (random.sample of a minibatch)")
+        it, val = 0, 1.0
+        while val > self.stop_val and it < it_max:
+            idx = torch.as_tensor(np.asarray(self.sampler(n, 1)).reshape(-1), dtype=torch.long, device=self.device)
+            loss = self.crit(self.model(F[idx, :self.nin]), F[idx, self.nin:self.nin + 2])
+            loss.backward()
+            self.opt.step()
+            self.opt.zero_grad()
+            val = self.beta * val + (1 - self.beta) * loss.item()
+            it += 1
+        self.total_steps += it
+        self.last = dict(iterations=it, val=val, launched=it)
+        return dict(self.last)
+
+    # -- the forward pass: device kernels on a GPU, PyTorch otherwise ----------------------------------
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _param_ptrs(self):
+        ps = list(self.model.parameters())
+        for p in ps:
+            if not p.is_contiguous() or p.dtype != torch.float32 or not p.is_cuda:
+                raise ValueError("model parameters must be contiguous float32 tensors on the trainer's device")
+        return [p.data_ptr() for p in ps]
+
+    def _push(self):
+        self._cl.check(self._lib.vboc_cls_set_params(self._h, *self._param_ptrs(), self._stream()))
+
+    @torch.no_grad()
+    def predict_labels(self, X, batch=1 << 15, logits=False):
+        """(labels uint8 [n] on the trainer's device, count of label 1) for the normalised float32 rows X [n, 2nq]:
+        argmax of the two logits, a tie gives 0 (:136-148).  logits=True appends the [n, 2] logits."""
+        X = self._rows(X)
+        n = X.shape[0]
+        if self._h is not None:
+            import ctypes
+            lab = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            lg = torch.empty((n, 2), dtype=torch.float32, device=self.device) if logits else None
+            cnt = ctypes.c_longlong()
+            self._push()
+            self._cl.check(self._lib.vboc_cls_eval(self._h, X.data_ptr() if n else None, n, X.shape[1] if n else 0,
+                                                   lab.data_ptr() if n else None,
+                                                   lg.data_ptr() if (logits and n) else None, ctypes.byref(cnt),
+                                                   self._stream()))
+            return (lab, int(cnt.value), lg) if logits else (lab, int(cnt.value))
+        out = torch.cat([self.model(X[i:i + batch]) for i in range(0, n, batch)]) if n else \
+            torch.zeros((0, 2), device=self.device)
+        lab = (out[:, 1] > out[:, 0]).to(torch.uint8)
+        return (lab, int(lab.sum().item()), out) if logits else (lab, int(lab.sum().item()))
+
+    @torch.no_grad()
+    def boundary_errors(self, X_test, mean, std, max_steps=None):
+        """The RMSE march (:150-176) of every held-out state: dict(err [m] float64, steps, flags, capped, rmse)."""
+        max_steps = max_steps or self.max_steps
+        X = np.ascontiguousarray(X_test, dtype=np.float64)
+        m = X.shape[0]
+        mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+        std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
+        if self._h is not None and self.nq in (2, 3):
+            Xd = torch.as_tensor(X).to(self.device)
+            err = torch.empty((m,), dtype=torch.float64, device=self.device)
+            steps = torch.empty((m,), dtype=torch.int32, device=self.device)
+            flags = torch.empty((m,), dtype=torch.uint8, device=self.device)
+            self._push()
+            if m:
+                self._cl.check(self._lib.vboc_cls_boundary(self._h, Xd.data_ptr(), m, self.nq, float(mean_t),
+                                                           float(std_t), max_steps, err.data_ptr(), steps.data_ptr(),
+                                                           flags.data_ptr(), self._stream()))
+            err, steps, flags = err.cpu().numpy(), steps.cpu().numpy(), flags.cpu().numpy()
+        else:
+            def classify(P):
+                out = self.model((torch.from_numpy(P).to(self.device) - mean_t) / std_t)
+                return (out[:, 1] > out[:, 0]).cpu().numpy()
+            err, steps, flags = march_reference(classify, X, mean, std, max_steps)
+        rmse = math.sqrt(np.sum(np.power(err, 2)) / m) if m else 0.0
+        return dict(err=err, steps=steps, flags=flags, capped=int(((flags >> 1) & 1).sum()), rmse=rmse)
+
+
+class HipClsTrainer(ClsTrainer):
+    """ClsTrainer's fit on the device kernels of csrc/cls.hip (libvboc_cls.so, include/vboc_cls.h): sampling,
+    forward, BCE, backward, Adam and the stop rule in three kernels per step, `poll` steps per HIP graph.  The torch
+    module stays the source of truth between fits; Adam's moments and step count live in the native trainer across
+    fits.  The minibatches are the native sampler's (Philox, random.sample's set method); `sample` advances it."""
+
+    def __init__(self, nq, device="cuda", graphs=True, poll=64, **kw):
+        super().__init__(nq, device, native_eval=True, **kw)
+        if self._h is None:
+            raise ValueError("HipClsTrainer needs a GPU, libvboc_cls.so and a supported shape")
+        self.use_graphs, self.poll = graphs, poll
+
+    def sample(self, n, steps=1):
+        out = torch.empty((steps, self.k), dtype=torch.int32, device=self.device)
+        self._cl.check(self._lib.vboc_cls_sample(self._h, n, steps, out.data_ptr(), self._stream()))
+        return out.cpu().numpy().astype(np.int64)
+
+    def fit(self, F, it_max):
+        import ctypes
+        F = self._rows(F)
+        n = F.shape[0]
+        if n < self.k:
+            raise ValueError(f"need at least {self.k} rows (random.sample of a minibatch)")
+        ptrs = self._param_ptrs()
+        self._push()
+        its, val, launched, ms = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+        run = self._cl.ClsRun(F=F.data_ptr(), n=n, ld=F.shape[1], it_max=it_max, val0=1.0, stop_val=self.stop_val,
+                              beta=self.beta, lr=self.lr, poll=self.poll, graphs=int(self.use_graphs),
+                              iterations=ctypes.addressof(its), val=ctypes.addressof(val),
+                              launched=ctypes.addressof(launched), kernel_ms=ctypes.addressof(ms))
+        self._cl.check(self._lib.vboc_cls_train(self._h, ctypes.byref(run), self._stream()))
+        self._cl.check(self._lib.vboc_cls_get_params(self._h, 0, *ptrs, self._stream()))
+        self.total_steps += launched.value
+        self.last = dict(iterations=its.value, val=val.value, launched=launched.value, fit_ms=ms.value)
+        return dict(iterations=its.value, val=val.value, launched=launched.value)
+
+    def moments(self):
+        """Adam's (exp_avg, exp_avg_sq) as lists of tensors in the model's parameter order (test hook)."""
+        out = []
+        for which in (1, 2):
+            ts = [torch.empty_like(p) for p in self.model.parameters()]
+            self._cl.check(self._lib.vboc_cls_get_params(self._h, which, *[t.data_ptr() for t in ts], self._stream()))
+            out.append(ts)
+        return out
+
+
+def make_cls_trainer(nq, device="cpu", native=False, **kw):
+    """The classifier of the HJR loop: ClsTrainer (PyTorch) by default; native=True selects HipClsTrainer on a GPU
+    for the shapes csrc/cls.hip implements (make_trainer's rule).  Either way a GPU run classifies and marches on the
+    device kernels."""
+    from . import clslib
+    dev = torch.device(device)
+    if native and dev.type == "cuda" and clslib.supported(2 * nq, kw.get("hidden", 100),
+                                                          kw.get("minibatch") or CLS_MINIBATCH[nq]):
+        return HipClsTrainer(nq, device, **kw)
+    return ClsTrainer(nq, device, **kw)

@@ -573,3 +573,131 @@ def cartesian_run(backend=None, num_test=1000, num_train=100000, out_dir=None, d
         torch.save(float(margin), os.path.join(out_dir, "margin_" + tag))
     return dict(X_test=X_test, X_train=X_train, fit=fit, rmse_train=rmse_train, rmse_test=rmse_test,
                 stats=(st_test, st_train), mean=mean, std=std, prune=pruned, safety_margin=margin)
+
+
+# ------------------------------------------------------------------------------------------------
+# the HJR loop (HJR/triplependulum_hjr.py:43-343, HJR/doublependulum_hjr.py, HJR/pendulum_hjr.py:40-190)
+# ------------------------------------------------------------------------------------------------
+# per system: candidates per set, time budget, loss_stop, minibatch, it_max = int(scale * B / minibatch), the
+# iteration cap, and whether the stop rule has the `iterbreak > 10` clause (the pendulum's has none, and no clock)
+HJR = {3: dict(B=12 ** 6, max_time=21600.0, loss_stop=5e-3, minibatch=4096, scale=2e3, cap=120, grace=True),
+       2: dict(B=25 ** 4, max_time=3600.0, loss_stop=5e-3, minibatch=4096, scale=2e3, cap=150, grace=True),
+       1: dict(B=100 ** 2, max_time=float("inf"), loss_stop=1e-3, minibatch=64, scale=1e2, cap=100, grace=False)}
+
+
+def hjr_continues(nq, pos_new, pos_old, iterbreak, elapsed=0.0, max_time=None):
+    """The outer `while` of the three drivers (triple :186, double :189, pendulum :115)."""
+    c = HJR[nq]
+    if not c["grace"]:
+        return pos_new <= pos_old and iterbreak < c["cap"]
+    max_time = c["max_time"] if max_time is None else max_time
+    return (pos_new <= pos_old or iterbreak > 10) and iterbreak < c["cap"] and elapsed < max_time
+
+
+def hjr_run(nq, X_test=None, max_time=None, B=None, hidden=100, max_iterations=None, seed=SEED, out_dir=None,
+            device="cuda", native=False, ocp_factory=None, it_max=None, minibatch=None, trainer=None):
+    """The HJR main block: first fit on the box labels, then per iteration the one-step OCP labels of a fresh
+    candidate set (hjr.hjr_labels_arrays), a refit with the same optimizer, the share of the test set classified
+    viable (the stop rule) and the RMSE march over the held-out states X_test (nq 2 and 3; the reference keeps the
+    march off its clock).  Quirk kept: pos_old = B (a count) before the first iteration, pos_new a fraction.
+    `ocp_factory(mean, std, params)` defaults to the hjr.OCP<sys> class; `trainer` to make_cls_trainer(native=...);
+    the candidate sets are ics.hjr_candidates (Philox streams 7-9).  it_max / minibatch override the driver's
+    constants (tests).  Returns dict(times, rmse, pos, fits, capped, iterations, trainer, mean, std, split)
+    and writes model_/mean_/std_<n>dof_hjr (and times_/rmse_<n>dof_hjr.npy for nq 2 and 3) into out_dir."""
+    import torch
+    from . import hjr as hjr_mod
+    from .ics import hjr_candidates
+    from .learn import make_cls_trainer
+    c = HJR[nq]
+    B = B or c["B"]
+    k = minibatch or c["minibatch"]
+    if it_max is None:
+        it_max = int(c["scale"] * B / k) + (0 if c["grace"] else 1)        # the pendulum's `it <= it_max`
+    if ocp_factory is None:
+        ocp_factory = {3: hjr_mod.OCPtriplependulum, 2: hjr_mod.OCPdoublependulum, 1: hjr_mod.OCPpendulum}[nq]
+    candidates = lambda nq_, kind, B_, it_=0: hjr_candidates(nq_, kind, B_, it_, seed)
+    tr = trainer or make_cls_trainer(nq, device, native=native, hidden=hidden, minibatch=k,
+                                     stop_val=c["loss_stop"], seed=seed % (1 << 31))
+    dev = tr.device if hasattr(tr, "device") else torch.device(device)
+    split = dict(labelling=0.0, fit=0.0, classify=0.0, march=0.0, fit_steps=0)
+    clock = time.perf_counter
+    start = clock()
+
+    def f32(X):
+        return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+
+    def timed(key, fn):
+        t = clock()
+        out = fn()
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        split[key] += clock() - t
+        return out
+
+    Xu_iter = candidates(nq, "init", B)
+    Xu_test = candidates(nq, "test", B)
+    Xf = f32(Xu_iter)
+    mean, std = torch.mean(Xf), torch.std(Xf)
+    Xt_norm = (f32(Xu_test) - mean) / std
+    q_lo, q_hi, v_hi = hjr_mod.THETA_MIN, hjr_mod.THETA_MAX, hjr_mod.DTHETA_MAX
+    inside = np.all((Xu_iter[:, :nq] >= q_lo) & (Xu_iter[:, :nq] <= q_hi), axis=1) & \
+        np.all((Xu_iter[:, nq:] >= -v_hi) & (Xu_iter[:, nq:] <= v_hi), axis=1)
+
+    def rows(Xn, lab1):
+        y = f32(np.c_[1 - lab1, lab1])
+        return torch.cat([Xn, y], dim=1).contiguous()
+
+    fits, pos, rmse, times, capped, kept = [], [], [], [], 0, []
+
+    def fit(F):
+        r = timed("fit", lambda: tr.fit(F, it_max))
+        split["fit_steps"] += r["iterations"]
+        fits.append(r)
+
+    def march():
+        nonlocal capped
+        if X_test is None or nq == 1:
+            return 0.0
+        t = clock()
+        r = timed("march", lambda: tr.boundary_errors(X_test, mean, std))
+        capped += r["capped"]
+        rmse.append(r["rmse"])
+        return clock() - t
+
+    fit(rows((Xf - mean) / std, inside.astype(np.int64)))
+    pos_old = Xu_iter.shape[0]
+    pos_new = timed("classify", lambda: tr.predict_labels(Xt_norm))[1] / B
+    pos.append(pos_new)
+    march()
+    times.append(clock() - start)            # :177: the first march is on the clock, the later ones are not
+    init_times, test_times, iterbreak = 0.0, 0.0, 0
+    while hjr_continues(nq, pos_new, pos_old, iterbreak, clock() - start - init_times - test_times, max_time) \
+            and (max_iterations is None or iterbreak < max_iterations):
+        iterbreak += 1
+        t = clock()
+        ocp = ocp_factory(mean.item(), std.item(), tr.model.parameters())
+        init_times += clock() - t
+        Xu_iter = candidates(nq, "iter", B, iterbreak)
+        Xn = (f32(Xu_iter) - mean) / std
+        y_pred = timed("classify", lambda: tr.predict_labels(Xn))[0].cpu().numpy()
+        keep, lab1 = timed("labelling", lambda: hjr_mod.hjr_labels_arrays(ocp, Xu_iter, y_pred))
+        kept.append((keep, lab1))
+        km = torch.from_numpy(keep).to(dev)
+        fit(rows(Xn[km], lab1[keep].astype(np.int64)))
+        pos_old = pos_new
+        pos_new = timed("classify", lambda: tr.predict_labels(Xt_norm))[1] / B
+        pos.append(pos_new)
+        del ocp
+        times.append(clock() - start - init_times - test_times)
+        test_times += march()
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        tag = f"{nq}dof_hjr"
+        torch.save({kk: v.detach().cpu() for kk, v in tr.model.state_dict().items()}, os.path.join(out_dir, f"model_{tag}"))
+        torch.save(mean.cpu(), os.path.join(out_dir, f"mean_{tag}"))
+        torch.save(std.cpu(), os.path.join(out_dir, f"std_{tag}"))
+        if nq > 1:
+            np.save(os.path.join(out_dir, f"times_{tag}.npy"), np.asarray(times))
+            np.save(os.path.join(out_dir, f"rmse_{tag}.npy"), np.asarray(rmse))
+    return dict(times=np.asarray(times), rmse=np.asarray(rmse), pos=np.asarray(pos), fits=fits, capped=capped,
+                iterations=iterbreak, kept=kept, trainer=tr, mean=mean, std=std, split=split)
