@@ -137,6 +137,18 @@ class _AlOcp:
         torch.cuda.synchronize(dev)
         return {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
 
+    def labels_guess(self, X, xg):
+        """(labels [B], trajectories [B, N+1, 2nq]) of the RTI step from the stage guesses xg for every state of X:
+        the AL loop's testing_guess.  X and xg may be float64 device tensors (PoolScorer.guess's output): they go to
+        the solver as they are, without visiting the host."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        T = lambda a: a.to(dev, torch.float64).contiguous() if torch.is_tensor(a) else \
+            torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+        out = self.solver.al_solve_device(self.spec, T(X), x_guess=T(xg))
+        torch.cuda.synchronize(dev)
+        return out["label"].cpu().numpy(), out["x"].cpu().numpy()
+
     def compute_problem_nnguess(self, q0, v0, model, mean, std):
         x0 = self._x0(q0, v0)   # :175
         r = self.compute_problem_nnguess_batch(x0[None], model, mean, std)

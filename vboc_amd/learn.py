@@ -504,11 +504,14 @@ CLS_MINIBATCH = {3: 4096, 2: 4096, 1: 64}       # n_minibatch of the three HJR d
 CLS_MAX_STEPS = 16384                           # bound of the outward march (the reference has none)
 
 
-def march_reference(classify, X_test, mean, std, max_steps=CLS_MAX_STEPS):
+def march_reference(classify, X_test, mean, std, max_steps=CLS_MAX_STEPS, outward_dims=None):
     """The march of HJR/triplependulum_hjr.py:150-176 restated over all rays at once.  `classify(P)` returns the
     labels of the float32 rows P [r, 2nq] (raw states; the normalisation (P - mean) / std is the caller's, inside
     classify).  Every ray accumulates its velocity step by step in float64, as the reference does; one call of
-    classify serves step k of every ray still marching.  Returns (err, steps, flags) as vboc_cls_boundary does."""
+    classify serves step k of every ray still marching.  Returns (err, steps, flags) as vboc_cls_boundary does.
+    outward_dims: the outward loop (start label 1) tests the norm of the first `outward_dims` velocity components
+    only, as the triple's AL march does (`norm([v0, v1])`, AL/triplependulum_al.py:221, :413); the inward loop and
+    the error keep the full norm.  None: the full norm in both loops."""
     X = np.asarray(X_test, dtype=np.float64)
     m, nq = X.shape[0], X.shape[1] // 2
     vt = X[:, nq:]
@@ -517,6 +520,8 @@ def march_reference(classify, X_test, mean, std, max_steps=CLS_MAX_STEPS):
         s2 = s2 + vt[:, j] * vt[:, j]
     vel_norm = np.sqrt(s2)
     label = np.asarray(classify(X.astype(np.float32))).astype(np.int64)
+    if outward_dims is not None:
+        return _march_outward_dims(classify, X, vel_norm, label, max_steps, outward_dims)
     with np.errstate(invalid="ignore", divide="ignore"):
         c = np.where(label[:, None] == 1, -1.0, 1.0) * ((1e-2 * vt) / vel_norm[:, None])
     v = vt.copy()
@@ -533,6 +538,41 @@ def march_reference(classify, X_test, mean, std, max_steps=CLS_MAX_STEPS):
         vn[act] = np.sqrt(q2)
         out = np.asarray(classify(np.c_[X[act, :nq], v[act]].astype(np.float32))).astype(np.int64)
         go = (out == label[act]) & (vn[act] > 1e-2)
+        cap = go & (steps[act] >= max_steps)
+        capped[act[cap]] = True
+        act = act[go & ~cap]
+    flags = (label | (capped.astype(np.int64) << 1)).astype(np.uint8)
+    return vel_norm - vn, steps, flags
+
+
+def _march_outward_dims(classify, X, vel_norm, label, max_steps, d):
+    """march_reference with the outward loop's stop test on the first d velocity components."""
+    m, nq = X.shape[0], X.shape[1] // 2
+    vt = X[:, nq:]
+
+    def norms(V):
+        full = V[:, 0] * V[:, 0]
+        for j in range(1, nq):
+            full = full + V[:, j] * V[:, j]
+        part = V[:, 0] * V[:, 0]
+        for j in range(1, d):
+            part = part + V[:, j] * V[:, j]
+        return np.sqrt(full), np.sqrt(part)
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = np.where(label[:, None] == 1, -1.0, 1.0) * ((1e-2 * vt) / vel_norm[:, None])
+    v = vt.copy()
+    vn = vel_norm.copy()
+    steps = np.zeros(m, dtype=np.int32)
+    capped = np.zeros(m, dtype=bool)
+    act = np.flatnonzero(np.where(label == 1, norms(vt)[1], vel_norm) > 1e-2)
+    while act.size:
+        v[act] = v[act] - c[act]
+        steps[act] += 1
+        full, part = norms(v[act])
+        vn[act] = full
+        out = np.asarray(classify(np.c_[X[act, :nq], v[act]].astype(np.float32))).astype(np.int64)
+        go = (out == label[act]) & (np.where(label[act] == 1, part, full) > 1e-2)
         cap = go & (steps[act] >= max_steps)
         capped[act[cap]] = True
         act = act[go & ~cap]
@@ -730,3 +770,241 @@ def make_cls_trainer(nq, device="cpu", native=False, **kw):
                                                           kw.get("minibatch") or CLS_MINIBATCH[nq]):
         return HipClsTrainer(nq, device, **kw)
     return ClsTrainer(nq, device, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# the AL loop's pool side (AL/triplependulum_al.py:253-281) and its guess network (:172-200, :353-387)
+# ------------------------------------------------------------------------------------------------
+POOL_BATCH = 1 << 15            # n_minibatch_model of the AL drivers
+
+
+class PoolScorer:
+    """The unlabeled pool's entropy, the top-B selection and the guess trajectories of the AL loop.
+
+    On a GPU (native=True, the default there) the three run on csrc/pool.hip (libvboc_pool.so, include/vboc_pool.h):
+    the pool is a float64 device tensor, scored, selected from and compacted without visiting the host, and the
+    guesses come out in the layout Solver.al_solve_device(x_guess=...) takes.  native=False is the reference's own
+    arithmetic on PyTorch / NumPy (the CPU path and the comparator): DataLoader batches of 2^15 through the module,
+    scipy.stats.entropy, np.argpartition(etp, -B)[-B:] sorted in reverse, al.nn_guess per state; the pool is a
+    NumPy array.  The parameters are pushed from the two torch modules at every call."""
+
+    def __init__(self, nq, cls_model, guess_model=None, device="cpu", native=None):
+        self.nq, self.nin = nq, 2 * nq
+        self.device = torch.device(device)
+        self.cls_model, self.guess_model = cls_model, guess_model
+        self.native = (self.device.type == "cuda") if native is None else bool(native)
+        self.calls = dict(entropy=[], select=[], guess=[])     # seconds per call (synchronised)
+        self._h = None
+        if self.native:
+            import ctypes
+            from . import poollib
+            if self.device.type != "cuda":
+                raise ValueError("the native PoolScorer runs on a GPU")
+            hidden = cls_model.linear_relu_stack[0].out_features
+            if not poollib.supported(self.nin, hidden):
+                raise ValueError(f"libvboc_pool.so does not implement inputs {self.nin}, hidden {hidden}")
+            self._pl, self._lib = poollib, poollib.load()       # a missing library is an error, not a fall-back
+            h = ctypes.c_void_p()
+            poollib.check(self._lib.vboc_pool_create(self.nin, hidden, ctypes.byref(h)))
+            self._h = h
+            self.hidden = hidden
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.vboc_pool_destroy(h)
+            self._h = None
+
+    # -- helpers --------------------------------------------------------------------------------------
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ptrs(self, model):
+        ps = list(model.parameters())
+        for p in ps:
+            if not p.is_contiguous() or p.dtype != torch.float32 or not p.is_cuda:
+                raise ValueError("model parameters must be contiguous float32 tensors on the scorer's device")
+        return [p.data_ptr() for p in ps]
+
+    def _timed(self, key, fn):
+        import time
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        t = time.perf_counter()
+        out = fn()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.calls[key].append(time.perf_counter() - t)
+        return out
+
+    def _dev_rows(self, t, dtype, cols, what):
+        """The native calls take raw pointers: a tensor of another dtype, device or layout would be read out of
+        bounds, so it is refused here."""
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or \
+                (t.dim() != 1 if cols is None else (t.dim() != 2 or t.shape[1] != cols)):
+            shape = "[n]" if cols is None else f"[n, {cols}]"
+            raise ValueError(f"{what} must be a contiguous {dtype} cuda tensor {shape} (see to_pool)")
+        return t
+
+    def to_pool(self, X):
+        """The pool in the scorer's own form: a float64 device tensor (native) or a float64 NumPy array."""
+        if self.native:
+            if torch.is_tensor(X):
+                return X.to(self.device, torch.float64).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64)).to(self.device)
+        return X.detach().cpu().double().numpy() if torch.is_tensor(X) else np.ascontiguousarray(X, dtype=np.float64)
+
+    # -- the entropy of every pool row (:253-264) -----------------------------------------------------
+    @torch.no_grad()
+    def entropy(self, X, mean, std, logits=False):
+        """etp of the rows of X [n, 2nq] (raw states): a float32 device tensor (native) or the reference's float64
+        array of float32 values.  logits=True returns (etp, logits [n, 2])."""
+        return self._timed("entropy", lambda: self._entropy(X, mean, std, logits))
+
+    def _entropy(self, X, mean, std, logits):
+        n = X.shape[0]
+        if self.native:
+            X = self._dev_rows(X, torch.float64, self.nin, "the pool")
+            etp = torch.empty((n,), dtype=torch.float32, device=self.device)
+            lg = torch.empty((n, 2), dtype=torch.float32, device=self.device) if logits else None
+            if n:
+                self._pl.check(self._lib.vboc_pool_set_classifier(self._h, *self._ptrs(self.cls_model), self._stream()))
+                self._pl.check(self._lib.vboc_pool_entropy(self._h, X.data_ptr(), n, float(mean), float(std),
+                                                           etp.data_ptr(), lg.data_ptr() if logits else None, None,
+                                                           self._stream()))
+            return (etp, lg) if logits else etp
+        from scipy.stats import entropy
+        from torch.utils.data import DataLoader
+        sigmoid = nn.Sigmoid()
+        etp = np.empty((n,))
+        lgs = []
+        mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+        std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
+        if n:
+            Xt = torch.from_numpy(np.asarray(X, dtype=np.float32)).to(self.device)
+            Xt = (Xt - mean_t) / std_t
+            for idx, batch in enumerate(DataLoader(Xt, batch_size=POOL_BATCH, shuffle=False)):
+                out = self.cls_model(batch)
+                prob_xu = sigmoid(out).cpu()
+                etp[POOL_BATCH * idx:min(POOL_BATCH * (idx + 1), n)] = entropy(prob_xu, axis=1)
+                if logits:
+                    lgs.append(out.cpu())
+        if logits:
+            return etp, (torch.cat(lgs) if lgs else torch.zeros((0, 2)))
+        return etp
+
+    # -- the B most uncertain rows and the pool without them (:267-281) -------------------------------
+    def select(self, etp, X, B):
+        """dict(idx [B] int64 NumPy, descending row index; scores [B] (etp[idx], NumPy); X_sel [B, 2nq] the rows in
+        that order; X_rest the other rows in their order; etpmax = max of the selected scores).  Native: a radix
+        select, ties at the B-th value to the lower row index, NaN above every number and etpmax NaN then; the torch
+        path is np.argpartition's choice."""
+        return self._timed("select", lambda: self._select(etp, X, B))
+
+    def _select(self, etp, X, B):
+        n = X.shape[0]
+        if B > n:
+            raise ValueError("B exceeds the pool (the caller clamps B to the pool's remainder)")
+        if B == 0:
+            return dict(idx=np.zeros(0, dtype=np.int64), scores=np.zeros(0), X_sel=X[:0], X_rest=X, etpmax=0.0)
+        if self.native:
+            import ctypes
+            X = self._dev_rows(X, torch.float64, self.nin, "the pool")
+            etp = self._dev_rows(etp, torch.float32, None, "etp")
+            if etp.shape[0] != n:
+                raise ValueError("etp and the pool differ in their row counts")
+            idx = torch.empty((B,), dtype=torch.int64, device=self.device)
+            X_sel = torch.empty((B, self.nin), dtype=torch.float64, device=self.device)
+            X_rest = torch.empty((n - B, self.nin), dtype=torch.float64, device=self.device)
+            mx = ctypes.c_float()
+            ptr = lambda t: t.data_ptr() if t.numel() else None
+            self._pl.check(self._lib.vboc_pool_select(self._h, ptr(etp), ptr(X), n, B, self.nin, ptr(idx), ptr(X_sel),
+                                                      ptr(X_rest), ctypes.byref(mx), self._stream()))
+            return dict(idx=idx.cpu().numpy(), scores=etp[idx].cpu().numpy(), X_sel=X_sel, X_rest=X_rest,
+                        etpmax=float(mx.value))
+        maxindex = np.argpartition(etp, -B)[-B:].tolist()
+        maxindex.sort(reverse=True)
+        etpmax = max(etp[maxindex])
+        idx = np.asarray(maxindex, dtype=np.int64)
+        return dict(idx=idx, scores=etp[idx], X_sel=X[idx], X_rest=np.delete(X, idx, 0), etpmax=float(etpmax))
+
+    # -- the guess network's trajectories (compute_problem_nnguess) -----------------------------------
+    @torch.no_grad()
+    def guess(self, X0, N, mean, std):
+        """x_guess [B, N + 1, 2nq] float64 for the states X0 [B, 2nq]: stage 0 = x0, stages 1..N the network's output
+        * std + mean.  Native: a device tensor; torch path: al.nn_guess per state, a NumPy array."""
+        return self._timed("guess", lambda: self._guess(X0, N, mean, std))
+
+    def _guess(self, X0, N, mean, std):
+        Bq = X0.shape[0]
+        if self.native:
+            outputs = self.guess_model.linear_relu_stack[4].out_features
+            if not self._pl.supported(self.nin, self.hidden, outputs) or outputs != self.nin * N:
+                raise ValueError(f"libvboc_pool.so does not implement guess outputs {outputs} for N {N}")
+            X0 = self.to_pool(X0)
+            xg = torch.empty((Bq, N + 1, self.nin), dtype=torch.float64, device=self.device)
+            if Bq:
+                self._pl.check(self._lib.vboc_pool_set_guess(self._h, outputs, *self._ptrs(self.guess_model),
+                                                             self._stream()))
+                self._pl.check(self._lib.vboc_pool_guess(self._h, X0.data_ptr(), Bq, N, float(mean), float(std),
+                                                         xg.data_ptr(), self._stream()))
+            return xg
+        from .al import nn_guess
+        X0 = np.asarray(X0, dtype=np.float64)
+        n = self.nq
+        mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+        std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
+        return np.stack([nn_guess(N, s[:n], s[n:], self.guess_model, mean_t, std_t) for s in X0]) if Bq else \
+            np.zeros((0, N + 1, 2 * n))
+
+
+class GuessTrainer:
+    """The guess network of the AL loop on PyTorch: NeuralNetCLS(2nq, hidden, 2nq N), MSELoss, Adam(lr), one
+    optimizer for the whole run; fit() is `while val > loss_stop and it <= it_max` with val from 1
+    (AL/triplependulum_al.py:172-200, :353-387).  Rows of a fit: a labelled-viable state's trajectory, (N + 1) 2nq
+    values: the state, then the targets; both are normalised with (. - mean) / std in float32.  seed=None leaves
+    torch's generator where it is (the reference builds this model right after the classifier); rng is the
+    random.Random both fits of the loop share."""
+
+    def __init__(self, nq, N, device="cpu", hidden=100, lr=1e-3, beta=0.95, stop_val=0.1, seed=None, rng=None):
+        import random
+        self.nq, self.nin, self.N = nq, 2 * nq, N
+        self.device = torch.device(device)
+        if seed is not None:
+            torch.manual_seed(seed)
+        self.hidden = hidden
+        self.model = NeuralNetCLS(self.nin, hidden, self.nin * N).to(self.device)
+        self.lr, self.beta, self.stop_val = lr, beta, stop_val
+        self.opt = torch.optim.Adam(self.model.parameters(), lr=lr)
+        self.crit = nn.MSELoss()
+        self.rng = rng if rng is not None else random.Random(seed)
+        self.total_steps = 0
+        self.last = None
+
+    def fit(self, T, mean, std, it_max, qt, max_steps=None):
+        """T [m, (N + 1) 2nq] float64 trajectories; qt the minibatch size asked for (clamped to m inside the loop, as
+        :180-181).  max_steps caps the steps below the reference's rule (measurements).  Returns dict(iterations,
+        val, qt)."""
+        T = np.asarray(T, dtype=np.float64).reshape(-1, (self.N + 1) * self.nin)
+        mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+        std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
+        T32 = torch.from_numpy(T.astype(np.float32)).to(self.device)
+        it, val = 0, 1
+        while val > self.stop_val and it <= it_max and (max_steps is None or it < max_steps):
+            if T.shape[0] < qt:
+                qt = T.shape[0]
+            ind = torch.as_tensor(self.rng.sample(range(T.shape[0]), qt), dtype=torch.long, device=self.device)
+            X_iter_tensor = T32[ind, :self.nin]
+            y_iter_tensor = T32[ind, self.nin:]
+            X_iter_tensor = (X_iter_tensor - mean_t) / std_t
+            y_iter_tensor = (y_iter_tensor - mean_t) / std_t
+            outputs = self.model(X_iter_tensor)
+            loss = self.crit(outputs, y_iter_tensor)
+            loss.backward()
+            self.opt.step()
+            self.opt.zero_grad()
+            val = self.beta * val + (1 - self.beta) * loss.item()
+            it += 1
+        self.total_steps += it
+        self.last = dict(iterations=it, val=val, qt=qt)
+        return dict(self.last)

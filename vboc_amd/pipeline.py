@@ -701,3 +701,233 @@ def hjr_run(nq, X_test=None, max_time=None, B=None, hidden=100, max_iterations=N
             np.save(os.path.join(out_dir, f"rmse_{tag}.npy"), np.asarray(rmse))
     return dict(times=np.asarray(times), rmse=np.asarray(rmse), pos=np.asarray(pos), fits=fits, capped=capped,
                 iterations=iterbreak, kept=kept, trainer=tr, mean=mean, std=std, split=split)
+
+
+# ------------------------------------------------------------------------------------------------
+# the AL loop (AL/triplependulum_al.py:65-432, AL/doublependulum_al.py:64-420)
+# ------------------------------------------------------------------------------------------------
+# per system: the initial labelled set, the query batch, the networks' hidden size, the pool's grid points per axis
+# (pool = gridp ** (2 nq) rows) and the time budget; both drivers: etp_stop, loss_stop, minibatch and
+# it_max = int(1e2 B / minibatch) with `it <= it_max`
+AL = {3: dict(N_init=6 ** 6, B=6 ** 6, hidden=500, gridp=15, max_time=21600.0),
+      2: dict(N_init=10 ** 4, B=10 ** 4, hidden=300, gridp=60, max_time=3450.0)}
+AL_ETP_STOP, AL_LOSS_STOP, AL_MINIBATCH = 0.1, 0.1, 4096
+
+
+def al_continues(etpmax, pool_rows, elapsed, max_time, etp_stop=AL_ETP_STOP):
+    """The outer `while` of both drivers (triple :241, double :238)."""
+    return (not (etpmax < etp_stop or pool_rows == 0)) and elapsed < max_time
+
+
+def al_default_pool(nq, spec, seed=SEED):
+    """The drivers' unlabeled pool: the triple draws gridp^6 uniform states in the widened box (:115-123,
+    al.unlabeled_states), the double scales an unscrambled Halton sequence of gridp^4 points to it (:112-120)."""
+    from .al import unlabeled_states
+    n = AL[nq]["gridp"] ** (2 * nq)
+    if nq == 3:
+        return unlabeled_states(spec, n, np.random.default_rng(seed))
+    from scipy.stats import qmc
+    v_min, v_max = -spec.dthetamax, spec.dthetamax
+    lo = [spec.thetamin] * nq + [v_min - (v_max - v_min) / 20] * nq
+    hi = [spec.thetamax] * nq + [v_max + (v_max - v_min) / 20] * nq
+    return qmc.scale(qmc.Halton(d=2 * nq, scramble=False).random(n=n), lo, hi)
+
+
+def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=None, minibatch=None, it_max=None,
+           max_iterations=None, max_time=None, seed=SEED, device="cuda", out_dir=None, scorer=None, native=None,
+           fit_steps=None):
+    """The AL main block for the triple (nq 3) and the double (nq 2) pendulum, statement by statement: the initial
+    labels of the pool's first N_init rows (`testing`), the first fits of the classifier and of the guess network,
+    then per iteration the entropy of the whole remaining pool, the B most uncertain rows and their removal, their
+    labels from the guess network's trajectories (`testing_guess`), both refits, the clock and the RMSE march.
+
+    pool: the unlabeled states [n, 2nq] (default al_default_pool).  ocp: an object with `spec`, `labels(X)` and
+    `labels_guess(X, xg)`, each -> (labels [b], trajectories [b, N + 1, 2nq]); default al.OCP<sys>INIT on `device`.
+    scorer: a learn.PoolScorer-like object (default: PoolScorer on the two trainers' modules; native=None runs the
+    device library on a GPU and the torch / NumPy path on the CPU).  fit_steps caps each fit's steps below the
+    reference's rule (measurements only).  On a GPU the pool lives on the device as float64; it is scored, selected
+    from and compacted there, and the guesses go to the solver without visiting the host.
+
+    The one deviation: a state whose label is 2 (neither solved nor a QP failure) makes the reference crash
+    (`testing` returns None); here it is dropped from the labelled set and counted in `labels[2]`.
+
+    Returns dict(times, rmse, etpmax per iteration; queries, scores: the per-iteration row indices into the pool as
+    it stood and their scores; labels: the count of each label; dropped; split: seconds in entropy, select, guess,
+    labelling, fit_cls, fit_guess, march; iterations; cls_states, guess_states: both networks' state dicts as they
+    stood at each iteration's query; batches: per iteration the queried states, their in-bounds mask and labels;
+    trainer, guess_trainer, scorer, mean, std, X_iter, pool, pool_rows) and writes mean_/std_<n>dof_al, times_/rmse_<n>dof_al.npy,
+    model_<n>dof and data_<n>dof_al.npy into out_dir."""
+    import math
+    import random
+    import torch
+    from . import al as al_mod
+    from .learn import ClsTrainer, GuessTrainer, PoolScorer, march_reference
+    c = AL[nq]
+    B = B or c["B"]
+    N_init = N_init or c["N_init"]
+    hidden = hidden or c["hidden"]
+    n_minibatch = minibatch or AL_MINIBATCH
+    if it_max is None:
+        it_max = int(1e2 * B / n_minibatch)
+    stop_time = c["max_time"] if max_time is None else max_time
+    dev = torch.device(device)
+    clock = time.perf_counter
+    start_time = clock()
+    if ocp is None:
+        ocp = {3: al_mod.OCPtriplependulumINIT, 2: al_mod.OCPdoublependulumINIT}[nq](dev.index or 0)
+    spec = ocp.spec
+    nx, N = spec.nx, spec.N
+    # quirk kept: ONE `random` stream serves both fits (the reference's module-level random.sample)
+    rng = random.Random(seed)
+    half = dict(n_new=0)
+
+    def cls_sampler(n, steps):
+        if nq == 2 and half["n_new"]:
+            # quirk kept (double :301-307): half of the minibatch from the old rows, half from the new ones
+            n_old = n - half["n_new"]
+            return np.array([rng.sample(range(n_old), int(n_minibatch / 2)) +
+                             rng.sample(range(n_old, n), int(n_minibatch / 2)) for _ in range(steps)], dtype=np.int64)
+        return np.array([rng.sample(range(n), n_minibatch) for _ in range(steps)], dtype=np.int64)
+
+    tr = ClsTrainer(nq, dev, hidden=hidden, minibatch=n_minibatch, stop_val=AL_LOSS_STOP, seed=seed % (1 << 31),
+                    sampler=cls_sampler, native_eval=False)
+    gt = GuessTrainer(nq, N, dev, hidden=hidden, stop_val=AL_LOSS_STOP, seed=None, rng=rng)
+    if scorer is None:
+        scorer = PoolScorer(nq, tr.model, gt.model, dev, native=native)
+    split = dict(entropy=0.0, select=0.0, guess=0.0, labelling=0.0, fit_cls=0.0, fit_guess=0.0, march=0.0,
+                 fit_cls_steps=0, fit_guess_steps=0)
+
+    def timed(key, fn):
+        t = clock()
+        out = fn()
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        split[key] += clock() - t
+        return out
+
+    if pool is None:
+        pool = al_default_pool(nq, spec, seed)
+    Xu_iter = scorer.to_pool(pool)
+    # quirk kept: mean / std over the whole pool, all columns, before the first N_init rows leave it (:125-126)
+    Xu_iter_tensor = Xu_iter.to(torch.float32) if torch.is_tensor(Xu_iter) else \
+        torch.from_numpy(Xu_iter.astype(np.float32)).to(dev)
+    mean, std = torch.mean(Xu_iter_tensor), torch.std(Xu_iter_tensor)
+    del Xu_iter_tensor
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        torch.save(mean.cpu(), os.path.join(out_dir, f"mean_{nq}dof_al"))
+        torch.save(std.cpu(), os.path.join(out_dir, f"std_{nq}dof_al"))
+    host = lambda A: A.cpu().numpy() if torch.is_tensor(A) else np.asarray(A)
+    counts = {0: 0, 1: 0, 2: 0}
+    batches = []            # per labelled batch: the states, the in-bounds mask, the labels (0 out of the box)
+
+    def testing(S_any, guess):
+        """testing / testing_guess over a batch: (rows [m, 2nq + 2], trajectories [mt, (N + 1) 2nq]); a state out of
+        the box is [.., 1, 0] without an OCP; label 1 -> [.., 0, 1] and its trajectory, label 0 -> [.., 1, 0]; label
+        2 is dropped."""
+        S = host(S_any)
+        # al.out_of_bounds for every row at once: a position outside [thetamin, thetamax] or a velocity outside
+        # [-dthetamax, dthetamax] on any joint
+        inb = np.all((S[:, :nq] >= spec.thetamin) & (S[:, :nq] <= spec.thetamax) &
+                     (S[:, nq:] >= -spec.dthetamax) & (S[:, nq:] <= spec.dthetamax), axis=1)
+        lab = np.zeros(S.shape[0], dtype=np.int64)
+        traj = np.zeros((S.shape[0], N + 1, nx))
+        if inb.any():
+            if torch.is_tensor(S_any):
+                S_in = S_any[torch.from_numpy(inb).to(S_any.device)].contiguous()
+            else:
+                S_in = S[inb]
+            if guess:
+                xg = timed("guess", lambda: scorer.guess(S_in, N, mean, std))
+                l, x = timed("labelling", lambda: ocp.labels_guess(S_in, xg))
+            else:
+                l, x = timed("labelling", lambda: ocp.labels(host(S_in)))
+            lab[inb], traj[inb] = np.asarray(l), np.asarray(x)
+        for v in (0, 1, 2):
+            counts[v] += int((lab == v).sum())
+        keep = lab != 2
+        rows = np.c_[S, lab != 1, lab == 1].astype(np.float64)[keep]
+        batches.append(dict(S=S, inb=inb, label=lab))
+        return rows, traj[lab == 1].reshape(-1, (N + 1) * nx), int((~keep).sum())
+
+    def fit_cls(X_iter, n_new=0):
+        half["n_new"] = n_new
+        Xn = (torch.from_numpy(X_iter[:, :nx].astype(np.float32)).to(dev) - mean) / std
+        F = torch.cat([Xn, torch.from_numpy(X_iter[:, nx:].astype(np.float32)).to(dev)], dim=1)
+        lim = it_max + 1 if fit_steps is None else min(it_max + 1, fit_steps)      # `it <= it_max`
+        r = timed("fit_cls", lambda: tr.fit(F, lim))
+        split["fit_cls_steps"] += r["iterations"]
+
+    def fit_guess(X_traj, qt):
+        r = timed("fit_guess", lambda: gt.fit(X_traj, mean, std, it_max, qt, max_steps=fit_steps))
+        split["fit_guess_steps"] += r["iterations"]
+
+    def march():
+        if X_test is None:
+            return float("nan")
+
+        @torch.no_grad()
+        def classify(P):
+            out = tr.model((torch.from_numpy(P).to(dev) - mean) / std)
+            return (out[:, 1] > out[:, 0]).cpu().numpy()
+        # quirk kept: the triple's outward loop tests norm([v0, v1]), two of three components (:221, :413)
+        err, _, flags = timed("march", lambda: march_reference(classify, X_test, mean, std,
+                                                               outward_dims=2 if nq == 3 else None))
+        return math.sqrt(np.sum(np.power(err, 2)) / len(err))
+
+    # Data generation: the first N_init rows of the pool, then they leave it (:133-140)
+    X_iter, X_traj, dropped = testing(Xu_iter[:N_init], guess=False)
+    Xu_iter = Xu_iter[N_init:]
+    if torch.is_tensor(Xu_iter):
+        Xu_iter = Xu_iter.contiguous()
+    fit_cls(X_iter)
+    fit_guess(X_traj, n_minibatch)
+    rmse = [march()]
+    times = [clock() - start_time]           # the march is on the clock
+    k, etpmax = 0, 1
+    etps, queries, scores, cls_states, guess_states = [], [], [], [], []
+    while al_continues(etpmax, Xu_iter.shape[0], clock() - start_time, stop_time) and \
+            (max_iterations is None or k < max_iterations):
+        if Xu_iter.shape[0] < B:
+            B = Xu_iter.shape[0]
+        cls_states.append({kk: v.detach().cpu().clone() for kk, v in tr.model.state_dict().items()})
+        guess_states.append({kk: v.detach().cpu().clone() for kk, v in gt.model.state_dict().items()})
+        etp = timed("entropy", lambda: scorer.entropy(Xu_iter, mean, std))
+        sel = timed("select", lambda: scorer.select(etp, Xu_iter, B))
+        etpmax = sel["etpmax"]               # over the selected rows (:272)
+        k += 1
+        elems, Xu_iter = sel["X_sel"], sel["X_rest"]
+        queries.append(sel["idx"])
+        scores.append(np.asarray(sel["scores"]))
+        etps.append(etpmax)
+        tmp1, tp, d = testing(elems, guess=True)
+        dropped += d
+        if nq == 3:
+            # quirk kept (triple :289-293): sliding windows; qt then also is the guess fit's minibatch
+            qt = B if len(X_traj) > B else len(X_traj)
+            qi = B if len(X_iter) > B else len(X_iter)
+            X_traj = np.concatenate([X_traj[qt:], tp])
+            X_iter = np.concatenate([X_iter[qi:], tmp1])
+            fit_cls(X_iter)
+        else:
+            # quirks kept (double :284-289): X_iter grows; `tkeep = [i for i in X_traj if i in ind]` compares
+            # lists with ints, so it is always empty - the draw still advances the shared random stream
+            X_iter = np.concatenate([X_iter, tmp1])
+            qn = n_minibatch if len(X_traj) > n_minibatch else len(X_traj)
+            rng.sample(range(len(X_traj)), qn)
+            X_traj = tp
+            fit_cls(X_iter, n_new=len(tmp1))
+            qt = n_minibatch
+        fit_guess(X_traj, qt)
+        times.append(clock() - start_time)
+        rmse.append(march())
+    if out_dir is not None:
+        np.save(os.path.join(out_dir, f"times_{nq}dof_al.npy"), np.asarray(times))
+        np.save(os.path.join(out_dir, f"rmse_{nq}dof_al.npy"), np.asarray(rmse))
+        torch.save({kk: v.detach().cpu() for kk, v in tr.model.state_dict().items()},
+                   os.path.join(out_dir, f"model_{nq}dof"))
+        np.save(os.path.join(out_dir, f"data_{nq}dof_al.npy"), np.asarray(X_iter))
+    return dict(times=np.asarray(times), rmse=np.asarray(rmse), etpmax=np.asarray(etps), queries=queries,
+                scores=scores, labels=dict(counts), dropped=dropped, split=split, iterations=k,
+                cls_states=cls_states, guess_states=guess_states, batches=batches[1:], trainer=tr, guess_trainer=gt,
+                scorer=scorer, mean=mean, std=std, X_iter=X_iter, pool=Xu_iter, pool_rows=int(Xu_iter.shape[0]))
