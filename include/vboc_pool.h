@@ -6,6 +6,7 @@
  *   AL/triplependulum_al.py:267-281  the B most uncertain rows (np.argpartition, sorted in reverse), their removal
  *                                    from the pool and etpmax
  *   AL/triplependulum_class_al.py:180-192  the guess network's trajectories (compute_problem_nnguess)
+ *   AL/triplependulum_al.py:204-227, :396-420  the RMSE march of the held-out states (vboc_pool_boundary)
  *   my_nn.py:4-18                    NeuralNetCLS (Linear-ReLU-Linear-ReLU-Linear)
  * Supported: inputs 2, 4 or 6; hidden 1..512 (padded inside the library to 64, 128, 256, 320 or 512 units, the
  * padded units exactly zero); guess outputs = inputs * N <= 640.  Other shapes return VBOC_POOL_EUNSUPPORTED.
@@ -57,6 +58,22 @@ int vboc_pool_select(vboc_pool_handle h, const float* etp, const double* X, long
  * vboc_pool_set_guess with outputs = inputs * N. */
 int vboc_pool_guess(vboc_pool_handle h, const double* X0, long long B, int N, float mean, float std, double* x_guess,
                     void* stream);
+
+/* The RMSE march (AL/triplependulum_al.py:204-227, :396-420; the double's twin) under the handle's classifier.
+ * X_test: device float64 [m][inputs] raw states, nq = inputs / 2.  The start label of a ray is l1 > l0 of its row.
+ * With vel_norm the float64 norm of the nq velocity components, c_i = (1e-2 v_i) / vel_norm is subtracted (start
+ * label 0) or added (start label 1) step by step in float64; point k is the velocity after k such steps, cast to
+ * float32, normalised in float32 and classified.  The ray ends at the first point whose label differs from the start
+ * label, whose stop norm is not > 1e-2 (a NaN ends it) or whose index is max_steps.  The stop norm is the full norm;
+ * with 1 <= outward_dims < nq the rays of start label 1 test the norm of the first outward_dims velocity components
+ * instead (the triple's `norm([v0, v1])`).  A ray whose stop norm is not > 1e-2 at the start takes no step.
+ * err (device float64 [m]) = vel_norm - the full norm at the stopping point; steps (device int32 [m]) the stopping
+ * index; flags (device uint8 [m]): bit 0 the start label, bit 1 "stopped by max_steps alone".  A point's label is
+ * exactly what vboc_pool_entropy writes to `labels` for a row holding that point's float32 values; a ray's result does
+ * not depend on m or on the other rays.  max_steps <= 0 selects 16384; max_steps > 2^20, m < 0 and outward_dims
+ * outside 0..nq are VBOC_POOL_EARG; m = 0 returns without a launch; inputs 2 is VBOC_POOL_EUNSUPPORTED. */
+int vboc_pool_boundary(vboc_pool_handle h, const double* X_test, int m, float mean, float std, int max_steps,
+                       int outward_dims, double* err, int* steps, unsigned char* flags, void* stream);
 
 const char* vboc_pool_last_error(void);
 

@@ -6,6 +6,8 @@ operations, the pool size and the entropy pass's rate against the FP32 matrix pe
 --fit-steps caps the minibatch steps of each fit (the reference's cap is int(1e2 B / 4096) + 1 per fit).
 --torch runs the pool operations on the torch / NumPy path of the same commit on the same GPU (the comparator: the
 reference's arithmetic).
+--march device | torch picks the RMSE march: the scorer's kernel (vboc_pool_boundary) or march_reference on the torch
+module (the comparator); auto is al_run's default.  With it the file name gains _march_<device|torch>.
 usage: python tools/al_loop.py --nq 3 --iters 1 --fit-steps 200 --out profiles
 """
 import argparse
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--fit-steps", type=int, default=200)
     ap.add_argument("--test", type=int, default=100, help="held-out rays of the RMSE march (0: no march)")
     ap.add_argument("--torch", action="store_true", help="pool operations on the torch / NumPy path")
+    ap.add_argument("--march", choices=("auto", "device", "torch"), default="auto", help="the RMSE march's path")
     ap.add_argument("--B", type=int, default=None)
     ap.add_argument("--pool", type=int, default=None, help="pool rows (default: the reference's gridp ** (2 nq))")
     ap.add_argument("--device", default="cuda")
@@ -48,7 +51,8 @@ def main():
         pool = unlabeled_states(AlSpec(a.nq), a.pool, rng)
     t = time.time()
     r = al_run(a.nq, X_test, pool=pool, B=a.B, N_init=a.B, max_iterations=a.iters, device=a.device,
-               native=not a.torch, fit_steps=a.fit_steps)
+               native=not a.torch, fit_steps=a.fit_steps,
+               device_march={"auto": None, "device": True, "torch": False}[a.march])
     wall = time.time() - t
     s, calls = r["split"], r["scorer"].calls
     B = a.B or c["B"]
@@ -61,6 +65,8 @@ def main():
                split={k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items()},
                entropy_call_s=[round(x, 5) for x in ent], select_call_s=[round(x, 5) for x in calls["select"]],
                guess_call_s=[round(x, 5) for x in calls["guess"]],
+               march="device" if r["device_march"] else "torch", test=a.test,
+               march_call_s=[round(x, 5) for x in r["march_s"]], capped=r["capped"],
                entropy_flop=flop, entropy_tflops=round(flop / max(ent[0], 1e-12) / 1e12, 3) if ent else None,
                entropy_share_of_fp32_matrix_peak=round(flop / max(ent[0], 1e-12) / FP32_MATRIX_PEAK, 4) if ent else None,
                labels=r["labels"], dropped=r["dropped"], etpmax=[float(e) for e in r["etpmax"]],
@@ -69,7 +75,8 @@ def main():
     print(json.dumps(out), flush=True)
     if a.out:
         os.makedirs(a.out, exist_ok=True)
-        name = f"al_loop_{'triple' if a.nq == 3 else 'double'}_{'torch' if a.torch else 'device'}.json"
+        name = f"al_loop_{'triple' if a.nq == 3 else 'double'}_{'torch' if a.torch else 'device'}" \
+               f"{'' if a.march == 'auto' else '_march_' + a.march}.json"
         with open(os.path.join(a.out, name), "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")

@@ -11,6 +11,9 @@
 //              staged: layer 0 has K <= 6, so each lane recomputes the four H1 values of its A fragment from its
 //              rows' inputs and the [W0 | b0] rows kept in LDS.  Epilogue: the two logits and the entropy, or (guess
 //              network) H2 to a scratch buffer.
+//   k_march    the RMSE march of the held-out states under the classifier (AL/triplependulum_al.py:204-227, :396-420):
+//              one ray per workgroup, 64 points per round through k_fwd's tile body (written a second time, so that
+//              k_fwd's compiled code stays what it was), the start labels from one k_fwd launch.
 //   k_out      the guess network's third layer over H2 (16 rows x 256 outputs per workgroup, k-ordered fma chains),
 //              out * std + mean, widened to float64 into stages 1..N; stage 0 is x0.
 //   selection  a radix select on the scores' bits: four (k_hist, k_pick) passes of 8 bits, then k_count (per-block
@@ -197,6 +200,225 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
     }
     __syncthreads();
   }
+}
+
+struct MarchArgs {
+  const float* W0b;           // the classifier's buffers, as FwdArgs has them
+  const float* Wf;
+  const float* b1;
+  const float* W2;
+  const float* b2;
+  const double* X;            // held-out states [m][NIN]
+  const unsigned char* start; // [m]: k_fwd's labels of X
+  double* err;                // [m]
+  int* steps;                 // [m]
+  unsigned char* flags;       // [m]
+  float mean, std;
+  int max_steps;
+  int od;                     // outward_dims: 0 = the full norm in both directions
+};
+
+// The RMSE march (AL/triplependulum_al.py:204-227, :396-420), one ray per workgroup: cls.hip's k_boundary at RT = 64
+// points per round under the wide classifier.  Thread r < RT forms point base + r + 1 by r + 1 sequential float64
+// subtractions from the round's base velocity (the reference's own accumulation) and writes its normalised float32
+// inputs to the staging tile `xs`; the tile body is k_fwd's, statement by statement, with its A rows read from that
+// tile, so a point's label is what k_fwd gives the same float32 row (same k order, same two-logit reduction).  The
+// ray's float64 state lives in LDS across the body.  The first point whose label differs from the start label, whose
+// stop norm is not > 1e-2 or whose index is max_steps ends the ray; rounds = ceil(max_steps / RT) is known at launch.
+template <int NIN, int NT>
+__global__ __launch_bounds__(256) void k_march(MarchArgs a) {
+  constexpr int HP = 64 * NT, TG = HP / 16, ST = stride0(NIN), NQ = NIN / 2;
+  __shared__ __attribute__((aligned(16))) float w0s[HP * ST];
+  __shared__ float red[4][RT][2];
+  __shared__ float xs[RT][NIN];         // the round's points, normalised
+  __shared__ double vb[NQ], vbn[NQ];    // the round's base velocity; point RT's, the next base
+  __shared__ double cst[NQ], vn0;       // the step c; vel_norm
+  __shared__ double vnl[RT];            // the points' full norms
+  __shared__ int stopl[RT];             // bit 0: label differs, bit 1: stop norm not > 1e-2, bit 2: index >= max_steps
+  __shared__ int firstl;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int ray = blockIdx.x;
+  const double* xr = a.X + (size_t)ray * NIN;
+  const int label = a.start[ray];
+  const bool partial = label == 1 && a.od >= 1 && a.od < NQ;    // the triple's `norm([v0, v1])` in the outward loop
+  {
+    double v0[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) v0[i] = xr[NQ + i];
+    double s2 = v0[0] * v0[0], p2 = v0[0] * v0[0];
+#pragma unroll
+    for (int i = 1; i < NQ; ++i) {
+      s2 += v0[i] * v0[i];
+      if (i < a.od) p2 += v0[i] * v0[i];
+    }
+    const double vel_norm = sqrt(s2);
+    const double sn = partial ? sqrt(p2) : vel_norm;
+    if (!(sn > 1e-2)) {     // no step taken; every thread of the workgroup sees the same values
+      if (tid == 0) {
+        a.err[ray] = 0.0;
+        a.steps[ray] = 0;
+        a.flags[ray] = (unsigned char)label;
+      }
+      return;
+    }
+    // `v0 - 1e-2 * X_test[i][3] / vel_norm`: (1e-2 * x) / vel_norm, subtracted for label 0 and added for label 1
+    if (tid < NQ) {
+      const double vt = xr[NQ + tid];
+      vb[tid] = vt;
+      cst[tid] = (label ? -1.0 : 1.0) * ((1e-2 * vt) / vel_norm);
+    }
+    if (tid == 0) vn0 = vel_norm;
+  }
+  for (int i = tid; i < HP * ST; i += 256) w0s[i] = a.W0b[i];
+  if (tid < RT) {           // the positions do not change along the ray
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) xs[tid][i] = ((float)xr[i] - a.mean) / a.std;
+  }
+  __syncthreads();
+  const int rounds = (a.max_steps + RT - 1) / RT;
+  for (int rd = 0; rd < rounds; ++rd) {
+    const int base = rd * RT;
+    if (tid < RT) {
+      double v[NQ], c[NQ];
+#pragma unroll
+      for (int i = 0; i < NQ; ++i) {
+        v[i] = vb[i];
+        c[i] = cst[i];
+      }
+      for (int k = 0; k <= tid; ++k) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) v[i] = v[i] - c[i];
+      }
+      double q2 = v[0] * v[0], p2 = v[0] * v[0];
+#pragma unroll
+      for (int i = 1; i < NQ; ++i) {
+        q2 += v[i] * v[i];
+        if (i < a.od) p2 += v[i] * v[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NQ; ++i) xs[tid][NQ + i] = ((float)v[i] - a.mean) / a.std;
+      const double vn = sqrt(q2);
+      const double sn = partial ? sqrt(p2) : vn;
+      vnl[tid] = vn;
+      stopl[tid] = ((!(sn > 1e-2)) << 1) | ((base + tid + 1 >= a.max_steps) << 2);
+      if (tid == RT - 1) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) vbn[i] = v[i];
+      }
+    }
+    __syncthreads();
+
+    // ---- k_fwd's tile body over the staging tile ----
+    float x[RB][NIN];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) x[rb][i] = xs[16 * rb + lr][i];
+    f4 acc[RB][NT];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int u = 0; u < NT; ++u) acc[rb][u] = f4{0.f, 0.f, 0.f, 0.f};
+    const float* bp = a.Wf + ((size_t)w * TG * 64 + lane) * 4;
+
+    auto group = [&](int t, const f4 (&bv)[NT]) {
+      const float* wk = w0s + (16 * t + 4 * lq) * ST;
+      float av[RB][4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float wc[NIN];
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) wc[i] = wk[s * ST + i];
+        const float bc = wk[s * ST + NIN];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+          float sum = 0.f;
+#pragma unroll
+          for (int i = 0; i < NIN; ++i) sum = fmaf(x[rb][i], wc[i], sum);
+          av[rb][s] = fmaxf(sum + bc, 0.f);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int u = 0; u < NT; ++u) acc[rb][u] = mfma(av[rb][s], bv[u][s], acc[rb][u]);
+    };
+
+    f4 b0[NT], b1[NT];
+#pragma unroll
+    for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256);
+    for (int t = 0; t < TG; t += 2) {
+#pragma unroll
+      for (int u = 0; u < NT; ++u) b1[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 1));
+      group(t, b0);
+      if (t + 2 < TG) {
+#pragma unroll
+        for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 2));
+      }
+      group(t + 1, b1);
+    }
+
+    float op[RB][4][2];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) op[rb][g][0] = op[rb][g][1] = 0.f;
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int j = 16 * (w + 4 * u) + lr;
+      const float bj = a.b1[j], w0 = a.W2[j], w1 = a.W2[HP + j];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float h = fmaxf(acc[rb][u][g] + bj, 0.f);
+          op[rb][g][0] = fmaf(h, w0, op[rb][g][0]);
+          op[rb][g][1] = fmaf(h, w1, op[rb][g][1]);
+        }
+    }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          op[rb][g][0] += __shfl_xor(op[rb][g][0], o);
+          op[rb][g][1] += __shfl_xor(op[rb][g][1], o);
+        }
+      }
+    if (lr == 0) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          red[w][16 * rb + 4 * lq + g][0] = op[rb][g][0];
+          red[w][16 * rb + 4 * lq + g][1] = op[rb][g][1];
+        }
+    }
+    __syncthreads();
+    // ---- the march's epilogue: wave 0 holds the round's RT points, one per lane ----
+    if (tid < RT) {
+      const int r = tid;
+      const float l0 = (((red[0][r][0] + red[1][r][0]) + red[2][r][0]) + red[3][r][0]) + a.b2[0];
+      const float l1 = (((red[0][r][1] + red[1][r][1]) + red[2][r][1]) + red[3][r][1]) + a.b2[1];
+      const int sb = stopl[r] | ((int)(l1 > l0) != label);
+      const unsigned long long any = __ballot(sb != 0);
+      const int first = any ? __ffsll((long long)any) - 1 : RT;
+      if (r == 0) firstl = first;
+      if (r == first) {
+        a.err[ray] = vn0 - vnl[r];
+        a.steps[ray] = base + r + 1;
+        a.flags[ray] = (unsigned char)(label | ((sb == 4) << 1));     // bit 1: stopped by max_steps alone
+      }
+    }
+    __syncthreads();
+    if (firstl < RT) return;      // uniform: every thread reads the same word after the barrier
+    if (tid < NQ) vb[tid] = vbn[tid];
+    __syncthreads();
+  }
+  // not reached: the last round holds index max_steps, whose bit 2 ends the ray
 }
 
 // torch layouts -> the padded buffers (H real hidden units; O outputs, OP the padded row length of W2t).  The
@@ -478,6 +700,8 @@ struct vboc_pool {
   size_t cntcap = 0;
   SelState* st = nullptr;
   unsigned* maxkey_host = nullptr;      // pinned
+  float* metp = nullptr;                // the march's start pass: etp [mcap], then the labels [mcap]
+  size_t mcap = 0;                      // rays
 };
 
 static thread_local std::string g_pool_err;
@@ -540,6 +764,19 @@ static int launch_fwd(const vboc_pool* h, FwdArgs& a, hipStream_t s) {
   return 0;
 }
 
+template <int NIN>
+static int launch_march_nin(const vboc_pool* h, const MarchArgs& a, int m, hipStream_t s) {
+  switch (h->NT) {
+    case 1: hipLaunchKernelGGL((k_march<NIN, 1>), dim3(m), dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_march<NIN, 2>), dim3(m), dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((k_march<NIN, 4>), dim3(m), dim3(256), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((k_march<NIN, 5>), dim3(m), dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((k_march<NIN, 8>), dim3(m), dim3(256), 0, s, a); break;
+    default: return pfail(VBOC_POOL_EUNSUPPORTED, "hidden size");
+  }
+  return 0;
+}
+
 extern "C" {
 
 const char* vboc_pool_last_error(void) { return g_pool_err.c_str(); }
@@ -569,7 +806,7 @@ int vboc_pool_destroy(vboc_pool_handle h) {
   (void)hipDeviceSynchronize();
   free_net(h->cls);
   free_net(h->gs);
-  void* bufs[] = {h->H2, h->cntA, h->cntE, h->st};
+  void* bufs[] = {h->H2, h->cntA, h->cntE, h->st, h->metp};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->maxkey_host) (void)hipHostFree(h->maxkey_host);
@@ -636,6 +873,44 @@ int vboc_pool_entropy(vboc_pool_handle h, const double* X, long long n, float me
   a.W0b = h->cls.W0b; a.Wf = h->cls.Wf; a.b1 = h->cls.b1; a.W2 = h->cls.W2; a.b2 = h->cls.b2;
   a.X = X; a.etp = etp; a.logits = logits; a.labels = labels; a.H2 = nullptr; a.n = n; a.mean = mean; a.std = std;
   return launch_fwd(h, a, (hipStream_t)stream);
+}
+
+int vboc_pool_boundary(vboc_pool_handle h, const double* X_test, int m, float mean, float std, int max_steps,
+                       int outward_dims, double* err, int* steps, unsigned char* flags, void* stream) {
+  if (!h) return pfail(VBOC_POOL_EARG, "null handle");
+  if (h->nin == 2) return pfail(VBOC_POOL_EUNSUPPORTED, "the march takes inputs 4 and 6");
+  if (m < 0) return pfail(VBOC_POOL_EARG, "m < 0");
+  if (outward_dims < 0 || outward_dims > h->nin / 2) return pfail(VBOC_POOL_EARG, "outward_dims outside 0..nq");
+  if (max_steps > (1 << 20)) return pfail(VBOC_POOL_EARG, "max_steps > 2^20");
+  if (max_steps <= 0) max_steps = 16384;
+  if (m == 0) return 0;
+  if (!X_test || !err || !steps || !flags) return pfail(VBOC_POOL_EARG, "null argument");
+  if (!h->cls.set) return pfail(VBOC_POOL_EARG, "vboc_pool_set_classifier has not been called");
+  hipStream_t s = (hipStream_t)stream;
+  if ((size_t)m > h->mcap) {
+    PCHK(hipStreamSynchronize(s));
+    if (h->metp) (void)hipFree(h->metp);
+    h->metp = nullptr;
+    h->mcap = 0;
+    PCHK(hipMalloc((void**)&h->metp, (sizeof(float) + 1) * (size_t)m));
+    h->mcap = (size_t)m;
+  }
+  unsigned char* start = (unsigned char*)(h->metp + h->mcap);
+  // the start labels: one forward pass over X_test itself
+  FwdArgs f;
+  memset(&f, 0, sizeof f);
+  f.W0b = h->cls.W0b; f.Wf = h->cls.Wf; f.b1 = h->cls.b1; f.W2 = h->cls.W2; f.b2 = h->cls.b2;
+  f.X = X_test; f.etp = h->metp; f.logits = nullptr; f.labels = start; f.H2 = nullptr; f.n = m; f.mean = mean;
+  f.std = std;
+  if (int rc = launch_fwd(h, f, s)) return rc;
+  MarchArgs a;
+  a.W0b = f.W0b; a.Wf = f.Wf; a.b1 = f.b1; a.W2 = f.W2; a.b2 = f.b2;
+  a.X = X_test; a.start = start; a.err = err; a.steps = steps; a.flags = flags; a.mean = mean; a.std = std;
+  a.max_steps = max_steps; a.od = outward_dims == h->nin / 2 ? 0 : outward_dims;
+  int rc = h->nin == 6 ? launch_march_nin<6>(h, a, m, s) : launch_march_nin<4>(h, a, m, s);
+  if (rc) return rc;
+  PCHK(hipGetLastError());
+  return 0;
 }
 
 int vboc_pool_select(vboc_pool_handle h, const float* etp, const double* X, long long n, long long B, int inputs,

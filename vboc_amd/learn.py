@@ -779,9 +779,9 @@ POOL_BATCH = 1 << 15            # n_minibatch_model of the AL drivers
 
 
 class PoolScorer:
-    """The unlabeled pool's entropy, the top-B selection and the guess trajectories of the AL loop.
+    """The unlabeled pool's entropy, the top-B selection, the guess trajectories and the RMSE march of the AL loop.
 
-    On a GPU (native=True, the default there) the three run on csrc/pool.hip (libvboc_pool.so, include/vboc_pool.h):
+    On a GPU (native=True, the default there) the four run on csrc/pool.hip (libvboc_pool.so, include/vboc_pool.h):
     the pool is a float64 device tensor, scored, selected from and compacted without visiting the host, and the
     guesses come out in the layout Solver.al_solve_device(x_guess=...) takes.  native=False is the reference's own
     arithmetic on PyTorch / NumPy (the CPU path and the comparator): DataLoader batches of 2^15 through the module,
@@ -793,7 +793,7 @@ class PoolScorer:
         self.device = torch.device(device)
         self.cls_model, self.guess_model = cls_model, guess_model
         self.native = (self.device.type == "cuda") if native is None else bool(native)
-        self.calls = dict(entropy=[], select=[], guess=[])     # seconds per call (synchronised)
+        self.calls = dict(entropy=[], select=[], guess=[], boundary=[])     # seconds per call (synchronised)
         self._h = None
         if self.native:
             import ctypes
@@ -892,6 +892,41 @@ class PoolScorer:
         if logits:
             return etp, (torch.cat(lgs) if lgs else torch.zeros((0, 2)))
         return etp
+
+    # -- the RMSE march of the held-out states (:204-227, :396-420) -----------------------------------
+    @torch.no_grad()
+    def boundary(self, X_test, mean, std, max_steps=None, outward_dims=None):
+        """ClsTrainer.boundary_errors' dict (err [m] float64, steps, flags, capped, rmse) for the raw states X_test
+        [m, 2nq] under the classifier.  outward_dims: march_reference's (the triple's AL march passes 2).  Native: one
+        vboc_pool_boundary call, every point labelled by the library's own forward pass; else march_reference on the
+        module."""
+        return self._timed("boundary", lambda: self._boundary(X_test, mean, std, max_steps or CLS_MAX_STEPS,
+                                                              outward_dims or None))
+
+    def _boundary(self, X_test, mean, std, max_steps, outward_dims):
+        X = self.to_pool(X_test)
+        m = X.shape[0]
+        if self.native:
+            X = self._dev_rows(X, torch.float64, self.nin, "X_test")
+            err = torch.empty((m,), dtype=torch.float64, device=self.device)
+            steps = torch.empty((m,), dtype=torch.int32, device=self.device)
+            flags = torch.empty((m,), dtype=torch.uint8, device=self.device)
+            if m:
+                self._pl.check(self._lib.vboc_pool_set_classifier(self._h, *self._ptrs(self.cls_model), self._stream()))
+                self._pl.check(self._lib.vboc_pool_boundary(self._h, X.data_ptr(), m, float(mean), float(std),
+                                                            max_steps, outward_dims or 0, err.data_ptr(),
+                                                            steps.data_ptr(), flags.data_ptr(), self._stream()))
+            err, steps, flags = err.cpu().numpy(), steps.cpu().numpy(), flags.cpu().numpy()
+        else:
+            mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+            std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
+
+            def classify(P):
+                out = self.cls_model((torch.from_numpy(P).to(self.device) - mean_t) / std_t)
+                return (out[:, 1] > out[:, 0]).cpu().numpy()
+            err, steps, flags = march_reference(classify, X, mean, std, max_steps, outward_dims)
+        rmse = math.sqrt(np.sum(np.power(err, 2)) / m) if m else 0.0
+        return dict(err=err, steps=steps, flags=flags, capped=int(((flags >> 1) & 1).sum()), rmse=rmse)
 
     # -- the B most uncertain rows and the pool without them (:267-281) -------------------------------
     def select(self, etp, X, B):

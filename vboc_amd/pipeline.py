@@ -735,7 +735,7 @@ def al_default_pool(nq, spec, seed=SEED):
 
 def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=None, minibatch=None, it_max=None,
            max_iterations=None, max_time=None, seed=SEED, device="cuda", out_dir=None, scorer=None, native=None,
-           fit_steps=None):
+           fit_steps=None, device_march=None):
     """The AL main block for the triple (nq 3) and the double (nq 2) pendulum, statement by statement: the initial
     labels of the pool's first N_init rows (`testing`), the first fits of the classifier and of the guess network,
     then per iteration the entropy of the whole remaining pool, the B most uncertain rows and their removal, their
@@ -746,12 +746,16 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
     scorer: a learn.PoolScorer-like object (default: PoolScorer on the two trainers' modules; native=None runs the
     device library on a GPU and the torch / NumPy path on the CPU).  fit_steps caps each fit's steps below the
     reference's rule (measurements only).  On a GPU the pool lives on the device as float64; it is scored, selected
-    from and compacted there, and the guesses go to the solver without visiting the host.
+    from and compacted there, and the guesses go to the solver without visiting the host.  device_march: None runs the
+    RMSE march through `scorer.boundary` (vboc_pool_boundary, the classifier's own width) when the scorer is native and
+    has one, else through march_reference on the torch module; False always takes the latter; True raises when the
+    scorer cannot march on the device.
 
     The one deviation: a state whose label is 2 (neither solved nor a QP failure) makes the reference crash
     (`testing` returns None); here it is dropped from the labelled set and counted in `labels[2]`.
 
-    Returns dict(times, rmse, etpmax per iteration; queries, scores: the per-iteration row indices into the pool as
+    Returns dict(times, rmse, etpmax per iteration; capped, march_s: per march the rays stopped by the bound of the
+    outward march alone (flags bit 1) and the seconds; queries, scores: the per-iteration row indices into the pool as
     it stood and their scores; labels: the count of each label; dropped; split: seconds in entropy, select, guess,
     labelling, fit_cls, fit_guess, march; iterations; cls_states, guess_states: both networks' state dicts as they
     stood at each iteration's query; batches: per iteration the queried states, their in-bounds mask and labels;
@@ -862,17 +866,34 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
         r = timed("fit_guess", lambda: gt.fit(X_traj, mean, std, it_max, qt, max_steps=fit_steps))
         split["fit_guess_steps"] += r["iterations"]
 
+    # the march on the device: the scorer's own call (vboc_pool_boundary); X_test is uploaded once, here
+    can_march = bool(getattr(scorer, "native", False)) and callable(getattr(scorer, "boundary", None))
+    if device_march and not can_march:
+        raise ValueError("device_march=True needs a native scorer with a `boundary` method")
+    use_device_march = can_march if device_march is None else bool(device_march)
+    X_test_dev = scorer.to_pool(X_test) if (use_device_march and X_test is not None) else None
+    capped, march_s = [], []
+
     def march():
         if X_test is None:
+            capped.append(0)
             return float("nan")
+        # quirk kept: the triple's outward loop tests norm([v0, v1]), two of three components (:221, :413)
+        od = 2 if nq == 3 else None
+        t = split["march"]
+        if use_device_march:
+            b = timed("march", lambda: scorer.boundary(X_test_dev, mean, std, outward_dims=od))
+            march_s.append(split["march"] - t)
+            capped.append(int(((b["flags"] >> 1) & 1).sum()))
+            return b["rmse"]
 
         @torch.no_grad()
         def classify(P):
             out = tr.model((torch.from_numpy(P).to(dev) - mean) / std)
             return (out[:, 1] > out[:, 0]).cpu().numpy()
-        # quirk kept: the triple's outward loop tests norm([v0, v1]), two of three components (:221, :413)
-        err, _, flags = timed("march", lambda: march_reference(classify, X_test, mean, std,
-                                                               outward_dims=2 if nq == 3 else None))
+        err, _, flags = timed("march", lambda: march_reference(classify, X_test, mean, std, outward_dims=od))
+        march_s.append(split["march"] - t)
+        capped.append(int(((flags >> 1) & 1).sum()))
         return math.sqrt(np.sum(np.power(err, 2)) / len(err))
 
     # Data generation: the first N_init rows of the pool, then they leave it (:133-140)
@@ -927,7 +948,8 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
         torch.save({kk: v.detach().cpu() for kk, v in tr.model.state_dict().items()},
                    os.path.join(out_dir, f"model_{nq}dof"))
         np.save(os.path.join(out_dir, f"data_{nq}dof_al.npy"), np.asarray(X_iter))
-    return dict(times=np.asarray(times), rmse=np.asarray(rmse), etpmax=np.asarray(etps), queries=queries,
+    return dict(times=np.asarray(times), rmse=np.asarray(rmse), etpmax=np.asarray(etps), capped=capped,
+                march_s=march_s, device_march=use_device_march, queries=queries,
                 scores=scores, labels=dict(counts), dropped=dropped, split=split, iterations=k,
                 cls_states=cls_states, guess_states=guess_states, batches=batches[1:], trainer=tr, guess_trainer=gt,
                 scorer=scorer, mean=mean, std=std, X_iter=X_iter, pool=Xu_iter, pool_rows=int(Xu_iter.shape[0]))

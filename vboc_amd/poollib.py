@@ -1,6 +1,6 @@
 """ctypes binding of libvboc_pool.so (include/vboc_pool.h): the pool side of the AL loop on the device - the
-classifier's entropy over the unlabeled pool, the top-B selection with the pool's compaction, and the guess network's
-trajectories.
+classifier's entropy over the unlabeled pool, the top-B selection with the pool's compaction, the guess network's
+trajectories, and the RMSE march of the held-out states under the classifier.
 
 `build()` compiles vboc_amd/csrc/pool.hip for gfx950 in-tree; `load()` raises when the library is missing (CPU runs
 use learn.PoolScorer's torch / NumPy path explicitly).
@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvboc_pool.so")
 SRC = os.path.join(HERE, "csrc", "pool.hip")
 EXPORTS = ("vboc_pool_create", "vboc_pool_destroy", "vboc_pool_set_classifier", "vboc_pool_set_guess",
-           "vboc_pool_entropy", "vboc_pool_select", "vboc_pool_guess", "vboc_pool_last_error")
+           "vboc_pool_entropy", "vboc_pool_boundary", "vboc_pool_select", "vboc_pool_guess", "vboc_pool_last_error")
 EARG, EHIP, EUNSUPPORTED = -1, -2, -3
 MAX_HIDDEN, MAX_OUTPUTS = 512, 640
 
@@ -53,6 +53,7 @@ def load():
     lib.vboc_pool_set_classifier.argtypes = [vp] + [vp] * 6 + [vp]
     lib.vboc_pool_set_guess.argtypes = [vp, ctypes.c_int] + [vp] * 6 + [vp]
     lib.vboc_pool_entropy.argtypes = [vp, vp, ll, f, f, vp, vp, vp, vp]
+    lib.vboc_pool_boundary.argtypes = [vp, vp, ctypes.c_int, f, f, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.vboc_pool_select.argtypes = [vp, vp, vp, ll, ll, ctypes.c_int, vp, vp, vp, ctypes.POINTER(f), vp]
     lib.vboc_pool_guess.argtypes = [vp, vp, ll, ctypes.c_int, f, f, vp, vp]
     _lib = lib
