@@ -14,9 +14,11 @@
 //   k_adam      the partial sums reduced in a fixed order, torch.optim.Adam's update, W1 repacked as MFMA fragments
 //
 // k_eval is the forward pass alone (labels, logits, the count of label 1); k_boundary marches one ray per
-// workgroup, 16 steps per round through the same forward pass.  Every reduction has a fixed order; a step whose gate
-// is 0 changes nothing; every loop has a static bound (the sampler's probes end because its table is half empty).
-// Hidden units 100..127 of the padded buffers stay exactly zero: their gradients are exact zeros.
+// workgroup, 16 steps per round through the same forward pass.  There is one forward pass: nn_common.h's forward_rows,
+// called by k_fwd_bwd (which also packs H1 for dW1) and by forward16 (k_eval, k_boundary).  Every reduction has a
+// fixed order; a step whose gate is 0 changes nothing; every loop has a static bound (the sampler's probes end because
+// its table is half empty).  Hidden units 100..127 of the padded buffers stay exactly zero: their gradients are exact
+// zeros.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -113,67 +115,18 @@ __global__ __launch_bounds__(256) void k_fwd_bwd(Args a) {
   }
   __syncthreads();
 
-  // H1 = relu(x W0' + b0), kept in LDS and written transposed for dW1
-  for (int c = tid; c < HP; c += 256) {
-    float wc[NIN];
-#pragma unroll
-    for (int i = 0; i < NIN; ++i) wc[i] = P[Ly::W0 + c * NIN + i];
-    const float bc = P[Ly::B0 + c];
-    float h[R2];
-#pragma unroll
-    for (int r = 0; r < R2; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < NIN; ++i) s = fmaf(xs[r * NIN + i], wc[i], s);
-      h[r] = fmaxf(s + bc, 0.f);
-      H1[r * LD + c] = h[r];
-    }
+  // the forward pass; H1 is also written transposed for dW1.  acc[u][g] = H2[row 4 lq + g][col 16 (w + 4u) + lr]
+  f4 acc[NT];
+  auto pack_h1 = [&](int c, const float(&h)[R2]) {
     f4* dst = (f4*)(a.H1p + pk(c, row0, a.Bt / 16));
 #pragma unroll
     for (int q = 0; q < 4; ++q) dst[16 * q] = f4{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
-  }
-  __syncthreads();
-
-  // A2 = H1 W1' on MFMA: wave w owns column tiles w and w + 4
-  f4 acc[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
-  gemm_rows<HP, NT, LD>(H1, a.Wf, w, lane, lr, lq, acc);
-  // acc[u][g] = A2[row 4 lq + g][col 16 (w + 4u) + lr]; H2 = relu(A2 + b1); the two logits' partial sums
-  float op[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) op[g][0] = op[g][1] = 0.f;
-#pragma unroll
-  for (int u = 0; u < NT; ++u) {
-    const int j = 16 * (w + 4 * u) + lr;
-    const float bj = P[Ly::B1 + j], w0 = P[Ly::W2 + j], w1 = P[Ly::W2 + HP + j];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float h = fmaxf(acc[u][g] + bj, 0.f);
-      acc[u][g] = h;
-      op[g][0] = fmaf(h, w0, op[g][0]);
-      op[g][1] = fmaf(h, w1, op[g][1]);
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      op[g][0] += __shfl_xor(op[g][0], o);
-      op[g][1] += __shfl_xor(op[g][1], o);
-    }
-  }
-  if (lr == 0) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      U.f.red[w][4 * lq + g][0] = op[g][0];
-      U.f.red[w][4 * lq + g][1] = op[g][1];
-    }
-  }
+  };
+  forward_rows<NIN, HP, 2, Ly>(P, a.Wf, xs, H1, &U.f.red[0][0][0], acc, pack_h1);
   __syncthreads();
   if (tid < 2 * R2) {
     const int r = tid >> 1, o = tid & 1;
-    const float s = ((U.f.red[0][r][o] + U.f.red[1][r][o]) + U.f.red[2][r][o]) + U.f.red[3][r][o];
+    const float s = out_sum<2, 1>(&U.f.red[0][0][0], r, o);
     const float x = s + P[Ly::B2 + o], y = ys[tid];
     // BCEWithLogitsLoss, mean over 2 Bt elements: max(x, 0) - x y + log1p(exp(-|x|)); d / dx = (sigmoid(x) - y) / (2 Bt)
     ls[tid] = (fmaxf(x, 0.f) - x * y) + log1pf(expf(-fabsf(x)));
@@ -434,62 +387,17 @@ struct FwdOnlyLds {
 };
 
 // The two logits of the 16 rows in L.xs (normalised inputs, written and barrier-synchronised by the caller) into
-// L.lg, with the training forward's arithmetic (k_fwd_bwd).  Called by all 256 threads; ends on a barrier.
+// L.lg, through the training forward's own code (forward_rows).  Called by all 256 threads; ends on a barrier.
 template <int NIN>
 __device__ __forceinline__ void forward16(const float* P, const float* Wf, FwdOnlyLds& L) {
   using Ly = Lay<NIN>;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  for (int c = tid; c < HP; c += 256) {
-    float wc[NIN];
-#pragma unroll
-    for (int i = 0; i < NIN; ++i) wc[i] = P[Ly::W0 + c * NIN + i];
-    const float bc = P[Ly::B0 + c];
-#pragma unroll
-    for (int r = 0; r < R2; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < NIN; ++i) s = fmaf(L.xs[r * NIN + i], wc[i], s);
-      L.H1[r * LD + c] = fmaxf(s + bc, 0.f);
-    }
-  }
-  __syncthreads();
+  const int tid = threadIdx.x;
   f4 acc[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
-  gemm_rows<HP, NT, LD>(L.H1, Wf, w, lane, lr, lq, acc);
-  float op[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) op[g][0] = op[g][1] = 0.f;
-#pragma unroll
-  for (int u = 0; u < NT; ++u) {
-    const int j = 16 * (w + 4 * u) + lr;
-    const float bj = P[Ly::B1 + j], w0 = P[Ly::W2 + j], w1 = P[Ly::W2 + HP + j];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float h = fmaxf(acc[u][g] + bj, 0.f);
-      op[g][0] = fmaf(h, w0, op[g][0]);
-      op[g][1] = fmaf(h, w1, op[g][1]);
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      op[g][0] += __shfl_xor(op[g][0], o);
-      op[g][1] += __shfl_xor(op[g][1], o);
-    }
-  }
-  if (lr == 0) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      L.red[w][4 * lq + g][0] = op[g][0];
-      L.red[w][4 * lq + g][1] = op[g][1];
-    }
-  }
+  forward_rows<NIN, HP, 2, Ly>(P, Wf, L.xs, L.H1, &L.red[0][0][0], acc);
   __syncthreads();
   if (tid < 2 * R2) {
     const int r = tid >> 1, o = tid & 1;
-    L.lg[r][o] = (((L.red[0][r][o] + L.red[1][r][o]) + L.red[2][r][o]) + L.red[3][r][o]) + P[Ly::B2 + o];
+    L.lg[r][o] = out_sum<2, 1>(&L.red[0][0][0], r, o) + P[Ly::B2 + o];
   }
   __syncthreads();
 }
@@ -565,9 +473,9 @@ struct MarchArgs {
 };
 
 // One ray per workgroup (HJR/triplependulum_hjr.py:150-176).  Round 0 classifies the start point; every later round
-// classifies the next 16 points of the ray: thread r < 16 forms point base + r + 1 by r + 1 sequential float64 steps
-// from the round's base velocity (the reference's own accumulation), casts it to float32 and normalises it in
-// float32.  The first point whose label differs, whose |v| <= 1e-2 or whose index is max_steps ends the march.
+// classifies the next 16 points of the ray: thread r < 16 forms point base + r + 1 from the round's base velocity
+// (nn_common.h's ray helpers, shared with pool.hip's march), casts it to float32 and normalises it in float32.  The
+// first point whose label differs, whose |v| <= 1e-2 or whose index is max_steps ends the march.
 template <int NIN>
 __global__ __launch_bounds__(256) void k_boundary(MarchArgs a) {
   constexpr int NQ = NIN / 2;
@@ -576,23 +484,18 @@ __global__ __launch_bounds__(256) void k_boundary(MarchArgs a) {
   __shared__ int stop[R2];
   const int tid = threadIdx.x, ray = blockIdx.x;
   const double* x = a.X + (size_t)ray * NIN;
-  double v0[NQ], c[NQ], v[NQ];
-  double s2 = 0.0;
+  double v0[NQ], c[NQ], v[NQ], sn;
 #pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    v0[i] = x[NQ + i];
-    s2 += v0[i] * v0[i];
-  }
-  const double vel_norm = sqrt(s2);
+  for (int i = 0; i < NQ; ++i) v0[i] = x[NQ + i];
+  const double vel_norm = ray_norm<NQ, true>(v0, 0, false, sn);
   // the start label, from the float32 cast of the row
   if (tid < R2 * NIN) L.xs[tid] = ((float)x[tid % NIN] - a.mean) / a.std;
   if (tid < NQ) vb[tid] = v0[tid];
   __syncthreads();
   forward16<NIN>(a.P, a.Wf, L);
   const int label = L.lg[0][1] > L.lg[0][0];
-  // `v0 - 1e-2 * X_test[i][3] / vel_norm`: (1e-2 * x) / vel_norm, subtracted for label 0 and added for label 1
 #pragma unroll
-  for (int i = 0; i < NQ; ++i) c[i] = (label ? -1.0 : 1.0) * ((1e-2 * v0[i]) / vel_norm);
+  for (int i = 0; i < NQ; ++i) c[i] = ray_step(v0[i], vel_norm, label);
   float xq[NQ];
 #pragma unroll
   for (int i = 0; i < NQ; ++i) xq[i] = ((float)x[i] - a.mean) / a.std;
@@ -605,18 +508,13 @@ __global__ __launch_bounds__(256) void k_boundary(MarchArgs a) {
       if (tid < R2) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i) v[i] = vb[i];
-        for (int k = 0; k <= tid; ++k) {
-#pragma unroll
-          for (int i = 0; i < NQ; ++i) v[i] = v[i] - c[i];
-        }
-        double q2 = 0.0;
+        ray_point<NQ>(v, c, tid);
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-          q2 += v[i] * v[i];
           L.xs[tid * NIN + i] = xq[i];
           L.xs[tid * NIN + NQ + i] = ((float)v[i] - a.mean) / a.std;
         }
-        vn = sqrt(q2);
+        vn = ray_norm<NQ, true>(v, 0, false, sn);
       }
       __syncthreads();
       forward16<NIN>(a.P, a.Wf, L);

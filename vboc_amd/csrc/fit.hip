@@ -18,7 +18,8 @@
 //               W1 rewritten as the packed MFMA fragments of the next step's two products
 //
 // Beside the step (VBOC/vboc.py:564-642): k_prune selects the global L1 pruning mask, k_adam holds masked entries at
-// zero during the refit under it, k_eval is the forward-only pass behind the RMSE and the safety margin.
+// zero during the refit under it, k_eval is the forward-only pass behind the RMSE and the safety margin.  k_fwd_bwd
+// and k_eval run one forward pass, nn_common.h's forward_rows (k_fwd_bwd also packs H1 for dW1).
 //
 // Every operand streamed from L2 / MALL (W1 twice, H1 and dH2 for dW1) is stored fragment-packed (pk()): a wave's
 // B (or A) fragment of one 16 x 16 block is 1 KB contiguous, so each load instruction moves whole 256-B lines.
@@ -123,57 +124,17 @@ __global__ __launch_bounds__(256) void k_fwd_bwd(Args a) {
   }
   __syncthreads();
 
-  // H1 = relu(x W0' + b0), kept in LDS and written transposed for dW1
-  for (int c = tid; c < HP; c += 256) {
-    float wc[NIN];
-#pragma unroll
-    for (int i = 0; i < NIN; ++i) wc[i] = P[Ly::W0 + c * NIN + i];
-    const float bc = P[Ly::B0 + c];
-    float h[R2];
-#pragma unroll
-    for (int r = 0; r < R2; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < NIN; ++i) s = fmaf(xs[r * NIN + i], wc[i], s);
-      h[r] = fmaxf(s + bc, 0.f);
-      H1[r * LD + c] = h[r];
-    }
+  // the forward pass; H1 is also written transposed for dW1.  acc[u][g] = H2[row 4 lq + g][col 16 (w + 4u) + lr]
+  f4 acc[NT];
+  auto pack_h1 = [&](int c, const float(&h)[R2]) {
     f4* dst = (f4*)(a.H1p + pk(c, row0, a.Bt / 16));
 #pragma unroll
     for (int q = 0; q < 4; ++q) dst[16 * q] = f4{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
-  }
-  __syncthreads();
-
-  // A2 = H1 W1' on MFMA: wave w owns column tiles w, w + 4, ...; MFMA step s of group t sums k = 16t + 4 lq + s
-  f4 acc[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
-  gemm_rows<HP, NT, LD>(H1, a.Wf, w, lane, lr, lq, acc);
-  // acc[u][g] = A2[row 4 lq + g][col 16 (w + 4u) + lr]; H2 = relu(A2 + b1); output partial sums
-  float op[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < NT; ++u) {
-    const int j = 16 * (w + 4 * u) + lr;
-    const float bj = P[Ly::B1 + j], wj = P[Ly::W2 + j];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float h = fmaxf(acc[u][g] + bj, 0.f);
-      acc[u][g] = h;
-      op[g] = fmaf(h, wj, op[g]);
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) op[g] += __shfl_xor(op[g], o);
-  }
-  if (lr == 0) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) red[w][4 * lq + g] = op[g];
-  }
+  };
+  forward_rows<NIN, HP, 1, Ly>(P, a.Wf, xs, H1, &red[0][0], acc, pack_h1);
   __syncthreads();
   if (tid < R2) {
-    const float s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    const float s = out_sum<1, 1>(&red[0][0], tid, 0);
     const float o = fmaxf(s + P[Ly::B2], 0.f);
     const float e = o - ys[tid];
     dout[tid] = o > 0.f ? e * (2.f / (float)a.Bt) : 0.f;     // d mean((o - y)^2) / d o, through the last ReLU
@@ -579,9 +540,9 @@ struct EvalArgs {
   int ld, nblk;
 };
 
-// Forward only, the training forward's arithmetic (k_fwd_bwd: the W0 layer, gemm_rows on Wf, the output layer), 16
-// contiguous rows per workgroup and round; the last block's rows are loaded with clamped indices and masked on
-// output.  Thread r < 16 keeps row r's running sums over the workgroup's blocks (in block order), thread 0 adds the
+// Forward only, through the training forward's own code (forward_rows: the W0 layer, gemm_rows on Wf, the output
+// layer), 16 contiguous rows per workgroup and round; the last block's rows are loaded with clamped indices and masked
+// on output.  Thread r < 16 keeps row r's running sums over the workgroup's blocks (in block order), thread 0 adds the
 // 16 in lane order: a fixed order throughout, no floating-point atomics.
 template <int NIN, int HP>
 __global__ __launch_bounds__(256) void k_eval(EvalArgs e) {
@@ -591,7 +552,7 @@ __global__ __launch_bounds__(256) void k_eval(EvalArgs e) {
   __shared__ __attribute__((aligned(16))) float H1[R2 * LD];
   __shared__ float xs[R2 * NIN], red[4][R2];
   __shared__ double ys[R2], rs[R2], rm[R2], rc[R2];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x;
   const float* P = e.P;
   double sse = 0.0, mg = -INFINITY, cn = 0.0;
   for (int blk = blockIdx.x; blk < e.nblk; blk += gridDim.x) {
@@ -604,44 +565,11 @@ __global__ __launch_bounds__(256) void k_eval(EvalArgs e) {
       ys[tid - 192] = e.y ? e.y[row] : (double)e.F[(size_t)row * e.ld + NIN];
     }
     __syncthreads();
-    for (int c = tid; c < HP; c += 256) {
-      float wc[NIN];
-#pragma unroll
-      for (int i = 0; i < NIN; ++i) wc[i] = P[Ly::W0 + c * NIN + i];
-      const float bc = P[Ly::B0 + c];
-#pragma unroll
-      for (int r = 0; r < R2; ++r) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) s = fmaf(xs[r * NIN + i], wc[i], s);
-        H1[r * LD + c] = fmaxf(s + bc, 0.f);
-      }
-    }
-    __syncthreads();
     f4 acc[NT];
-#pragma unroll
-    for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
-    gemm_rows<HP, NT, LD>(H1, e.Wf, w, lane, lr, lq, acc);
-    float op[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      const int j = 16 * (w + 4 * u) + lr;
-      const float bj = P[Ly::B1 + j], wj = P[Ly::W2 + j];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) op[g] = fmaf(fmaxf(acc[u][g] + bj, 0.f), wj, op[g]);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) op[g] += __shfl_xor(op[g], o);
-    }
-    if (lr == 0) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) red[w][4 * lq + g] = op[g];
-    }
+    forward_rows<NIN, HP, 1, Ly>(P, e.Wf, xs, H1, &red[0][0], acc);
     __syncthreads();
     if (tid < R2 && row0 + tid < e.n) {
-      const float s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+      const float s = out_sum<1, 1>(&red[0][0], tid, 0);
       const float o = fmaxf(s + P[Ly::B2], 0.f);
       if (e.out) e.out[row0 + tid] = o;
       const double d = (double)o - ys[tid];

@@ -1,7 +1,10 @@
-// Device helpers shared by the two NN trainers (fit.hip: the VBOC regressor, cls.hip: the HJR / AL classifier): the
-// exact-f32 MFMA wrapper and its fragment-packed storage, the Philox minibatch sampler (random.sample's set method)
-// and torch.optim.Adam's single-tensor update.  Each trainer is its own translation unit and includes this once;
-// the sampler is templated on the trainer's argument record (fields st->seed, st->draws, n, n_new, Bt).
+// Device helpers shared by the three NN libraries (fit.hip: the VBOC regressor, cls.hip: the HJR / AL classifier,
+// pool.hip: the AL pool): the exact-f32 MFMA wrapper and its fragment-packed storage, the Philox minibatch sampler
+// (random.sample's set method), torch.optim.Adam's single-tensor update, the trainers' 16-row forward pass
+// (layer0_rows, gemm_rows, forward_rows), the output stage of every forward kernel of the three files (out_partials,
+// out_sum) and the float64 ray arithmetic of the two RMSE marches (ray_step, ray_point, ray_norm).  Each library is its
+// own translation unit with its own compile flags and includes this once; the sampler is templated on the trainer's
+// argument record (fields st->seed, st->draws, n, n_new, Bt).
 #ifndef VBOC_NN_COMMON_H
 #define VBOC_NN_COMMON_H
 
@@ -265,6 +268,147 @@ __device__ __forceinline__ void gemm_rows(const float* A, const float* B, int w,
     }
     mfma_group<NT, LD>(A, t + 1, lr, lq, b1, acc);
   }
+}
+
+// Layer 0 of the trainers' 16-row forward pass: H1 = relu(x W0' + b0) into LDS at row stride LD, one hidden column
+// per thread (k-ordered fma chain over the inputs).  xs holds the rows' inputs [16][NIN]; store(c, h) receives column
+// c's 16 values (k_fwd_bwd packs them for dW1; the forward-only kernels' NoStore does nothing).  The caller's barriers
+// stand before and after.
+struct NoStore {
+  __device__ __forceinline__ void operator()(int, const float (&)[16]) const {}
+};
+template <int NIN, int HP, int LD, class Store>
+__device__ __forceinline__ void layer0_rows(const float* W0, const float* b0, const float* xs, float* H1,
+                                            Store&& store) {
+  for (int c = threadIdx.x; c < HP; c += 256) {
+    float wc[NIN];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) wc[i] = W0[c * NIN + i];
+    const float bc = b0[c];
+    float h[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) s = fmaf(xs[r * NIN + i], wc[i], s);
+      h[r] = fmaxf(s + bc, 0.f);
+      H1[r * LD + c] = h[r];
+    }
+    store(c, h);
+  }
+}
+
+// The output stage after the hidden product, for RB blocks of 16 rows and NO outputs: acc[rb][u][g] holds
+// A2[row 16 rb + 4 lq + g][col j = 16 (w + 4u) + lr].  acc becomes H2 = relu(A2 + b1) (the backward half reads it),
+// each output's partial sum runs over the wave's columns in u order (one fma chain), then over the 16 lanes of a
+// row by xor shuffles; lane lr == 0 writes red[w][row][o] (red is [4][16 RB][NO]).  b1 starts at Pb[ob1], W2
+// ([NO][ldw]) at Pw[ow2]: the trainers keep both at constant offsets of one buffer, and given this way the offsets
+// fold into the loads.  The caller puts a barrier between this and out_sum.
+template <int NO, int RB, int NT>
+__device__ __forceinline__ void out_partials(f4 (&acc)[RB][NT], const float* Pb, int ob1, const float* Pw, int ow2,
+                                             int ldw, int w, int lr, int lq, float* red) {
+  float op[RB][4][NO];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int o = 0; o < NO; ++o) op[rb][g][o] = 0.f;
+#pragma unroll
+  for (int u = 0; u < NT; ++u) {
+    const int j = 16 * (w + 4 * u) + lr;
+    const float bj = Pb[ob1 + j];
+    float wj[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) wj[o] = Pw[ow2 + o * ldw + j];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float h = fmaxf(acc[rb][u][g] + bj, 0.f);
+        acc[rb][u][g] = h;
+#pragma unroll
+        for (int o = 0; o < NO; ++o) op[rb][g][o] = fmaf(h, wj[o], op[rb][g][o]);
+      }
+  }
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1)
+#pragma unroll
+        for (int o = 0; o < NO; ++o) op[rb][g][o] += __shfl_xor(op[rb][g][o], d);
+    }
+  if (lr == 0) {
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int o = 0; o < NO; ++o) red[((w * RB + rb) * 16 + 4 * lq + g) * NO + o] = op[rb][g][o];
+  }
+}
+
+// output o of row r over the four waves, in wave order (the output bias is the caller's)
+template <int NO, int RB>
+__device__ __forceinline__ float out_sum(const float* red, int r, int o) {
+  constexpr int W = 16 * RB * NO;
+  return ((red[r * NO + o] + red[W + r * NO + o]) + red[2 * W + r * NO + o]) + red[3 * W + r * NO + o];
+}
+
+// The trainers' forward pass over 16 rows, called by all 256 threads: layer 0 into H1 (row stride HP + 4), a barrier,
+// H2 = relu(H1 W1' + b1) on MFMA (wave w owns column tiles w + 4u; acc keeps H2 for the backward half) and the NO
+// outputs' per-wave partials into red [4][16][NO].  Ly gives the offsets W0, B0, B1, W2 in the parameter buffer P.
+// xs was written before a barrier of the caller's, and a barrier of the caller's stands between this and out_sum.
+template <int NIN, int HP, int NO, class Ly, class Store = NoStore>
+__device__ __forceinline__ void forward_rows(const float* P, const float* Wf, const float* xs, float* H1, float* red,
+                                             f4 (&acc)[HP / 64], Store&& store = Store()) {
+  constexpr int NT = HP / 64, LD = HP + 4;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
+  layer0_rows<NIN, HP, LD>(P + Ly::W0, P + Ly::B0, xs, H1, store);
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < NT; ++u) acc[u] = f4{0.f, 0.f, 0.f, 0.f};
+  gemm_rows<HP, NT, LD>(H1, Wf, w, lane, lr, lq, acc);
+  out_partials<NO, 1, NT>(reinterpret_cast<f4(&)[1][NT]>(acc), P, Ly::B1, P, Ly::W2, HP, w, lr, lq, red);
+}
+
+// The float64 ray arithmetic of the two RMSE marches (HJR/triplependulum_hjr.py:150-176, AL/triplependulum_al.py:
+// 204-227).
+//
+// `v0 - 1e-2 * X_test[i][3] / vel_norm`: (1e-2 * x) / vel_norm, subtracted for label 0 and added for label 1
+__device__ __forceinline__ double ray_step(double v0, double vel_norm, int label) {
+  return (label ? -1.0 : 1.0) * ((1e-2 * v0) / vel_norm);
+}
+
+// the velocity of point r + 1 past the base v: r + 1 sequential subtractions (the reference's own accumulation)
+template <int NQ>
+__device__ __forceinline__ void ray_point(double (&v)[NQ], const double (&c)[NQ], int r) {
+  for (int k = 0; k <= r; ++k) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) v[i] = v[i] - c[i];
+  }
+}
+
+// |v| (NQ >= 2); `sn` is the norm the stop test takes: |v[0 .. od)| where `partial` (then 1 <= od < NQ), else |v|
+// itself.  The sum of squares starts from v0^2 + v1^2 and takes the later terms in index order.  FUSED = false (pool.hip,
+// compiled without contraction) rounds every product and every sum, as NumPy does.  FUSED = true (cls.hip) is what
+// contraction made of the same sum when k_boundary was written, fma(v_i, v_i, ...) onto a rounded v1^2, written out so
+// that the recorded marches do not rest on the compiler choosing the same products again.
+template <int NQ, bool FUSED>
+__device__ __forceinline__ double ray_norm(const double (&v)[NQ], int od, bool partial, double& sn) {
+  auto add_sq = [](double s, double x) { return FUSED ? fma(x, x, s) : s + x * x; };
+  double q2 = add_sq(v[1] * v[1], v[0]);
+  double p2 = od == 1 ? v[0] * v[0] : q2;
+#pragma unroll
+  for (int i = 2; i < NQ; ++i) {
+    q2 = add_sq(q2, v[i]);
+    if (i < od) p2 = add_sq(p2, v[i]);
+  }
+  const double vn = sqrt(q2);
+  sn = partial ? sqrt(p2) : vn;
+  return vn;
 }
 
 // Adam (torch.optim.Adam, single-tensor path, betas (0.9, 0.999), eps 1e-8, no weight decay):

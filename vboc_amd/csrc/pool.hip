@@ -12,8 +12,8 @@
 //              rows' inputs and the [W0 | b0] rows kept in LDS.  Epilogue: the two logits and the entropy, or (guess
 //              network) H2 to a scratch buffer.
 //   k_march    the RMSE march of the held-out states under the classifier (AL/triplependulum_al.py:204-227, :396-420):
-//              one ray per workgroup, 64 points per round through k_fwd's tile body (written a second time, so that
-//              k_fwd's compiled code stays what it was), the start labels from one k_fwd launch.
+//              one ray per workgroup, 64 points per round through k_fwd's tile body (tile_gemm here, out_partials
+//              and out_sum in nn_common.h: one copy for both kernels), the start labels from one k_fwd launch.
 //   k_out      the guess network's third layer over H2 (16 rows x 256 outputs per workgroup, k-ordered fma chains),
 //              out * std + mean, widened to float64 into stages 1..N; stage 0 is x0.
 //   selection  a radix select on the scores' bits: four (k_hist, k_pick) passes of 8 bits, then k_count (per-block
@@ -62,9 +62,66 @@ struct FwdArgs {
 
 __device__ __forceinline__ float entr(float q) { return q == 0.f ? 0.f : -(q * logf(q)); }
 
+// One k group of 16 of the 64-row tile: the A fragment H1[16 rb + lr][16 t + 4 lq + s] recomputed from the lane's rows
+// x and the [W0 | b0] rows in LDS, then MFMA step s sums k = 16 t + 4 lq + s.
+template <int NIN, int NT>
+__device__ __forceinline__ void tile_group(const float (&x)[RB][NIN], const float* w0s, int t, int lq,
+                                           const f4 (&bv)[NT], f4 (&acc)[RB][NT]) {
+  constexpr int ST = stride0(NIN);
+  const float* wk = w0s + (16 * t + 4 * lq) * ST;
+  float av[RB][4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float wc[NIN];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) wc[i] = wk[s * ST + i];
+    const float bc = wk[s * ST + NIN];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) sum = fmaf(x[rb][i], wc[i], sum);
+      av[rb][s] = fmaxf(sum + bc, 0.f);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int u = 0; u < NT; ++u) acc[rb][u] = mfma(av[rb][s], bv[u][s], acc[rb][u]);
+}
+
+// The 64-row tile body shared by k_fwd and k_march: acc = H1 W1' for the lane's A rows x[rb] = row 16 rb + lr
+// (normalised inputs), wave w's column tiles w + 4u.  Two register sets of B fragments alternate, as in gemm_rows.
+// The logits follow through nn_common.h's out_partials / out_sum, so a row's logits are the same bits in both kernels.
+template <int NIN, int NT>
+__device__ __forceinline__ void tile_gemm(const float (&x)[RB][NIN], const float* w0s, const float* Wf, int w,
+                                          int lane, int lq, f4 (&acc)[RB][NT]) {
+  constexpr int TG = 4 * NT;      // k groups of 16; even
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int u = 0; u < NT; ++u) acc[rb][u] = f4{0.f, 0.f, 0.f, 0.f};
+  const float* bp = Wf + ((size_t)w * TG * 64 + lane) * 4;      // tile u: + u * 4 TG * 256, group t: + 256 t
+  f4 b0[NT], b1[NT];
+#pragma unroll
+  for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256);
+  for (int t = 0; t < TG; t += 2) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u) b1[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 1));
+    tile_group<NIN, NT>(x, w0s, t, lq, b0, acc);
+    if (t + 2 < TG) {
+#pragma unroll
+      for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 2));
+    }
+    tile_group<NIN, NT>(x, w0s, t + 1, lq, b1, acc);
+  }
+}
+
 template <int NIN, int NT>
 __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
-  constexpr int HP = 64 * NT, TG = HP / 16, ST = stride0(NIN);
+  constexpr int HP = 64 * NT, ST = stride0(NIN);
   __shared__ __attribute__((aligned(16))) float w0s[HP * ST];
   __shared__ float red[4][RT][2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
@@ -82,51 +139,7 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
       for (int i = 0; i < NIN; ++i) x[rb][i] = ((float)a.X[(size_t)row * NIN + i] - a.mean) / a.std;
     }
     f4 acc[RB][NT];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int u = 0; u < NT; ++u) acc[rb][u] = f4{0.f, 0.f, 0.f, 0.f};
-    const float* bp = a.Wf + ((size_t)w * TG * 64 + lane) * 4;      // tile u: + u * 4 TG * 256, group t: + 256 t
-
-    // one k group of 16: the A fragment H1[16 rb + lr][16 t + 4 lq + s] recomputed, then step s sums k = 16 t + 4 lq + s
-    auto group = [&](int t, const f4 (&bv)[NT]) {
-      const float* wk = w0s + (16 * t + 4 * lq) * ST;
-      float av[RB][4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float wc[NIN];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) wc[i] = wk[s * ST + i];
-        const float bc = wk[s * ST + NIN];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          float sum = 0.f;
-#pragma unroll
-          for (int i = 0; i < NIN; ++i) sum = fmaf(x[rb][i], wc[i], sum);
-          av[rb][s] = fmaxf(sum + bc, 0.f);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int u = 0; u < NT; ++u) acc[rb][u] = mfma(av[rb][s], bv[u][s], acc[rb][u]);
-    };
-
-    f4 b0[NT], b1[NT];
-#pragma unroll
-    for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256);
-    for (int t = 0; t < TG; t += 2) {       // TG = 4 NT is even
-#pragma unroll
-      for (int u = 0; u < NT; ++u) b1[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 1));
-      group(t, b0);
-      if (t + 2 < TG) {
-#pragma unroll
-        for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 2));
-      }
-      group(t + 1, b1);
-    }
+    tile_gemm<NIN, NT>(x, w0s, a.Wf, w, lane, lq, acc);
 
     // acc[rb][u][g] = A2[row 16 rb + 4 lq + g][col 16 (w + 4u) + lr]
     if (a.H2) {
@@ -144,49 +157,13 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
       }
       continue;
     }
-    float op[RB][4][2];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) op[rb][g][0] = op[rb][g][1] = 0.f;
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      const int j = 16 * (w + 4 * u) + lr;
-      const float bj = a.b1[j], w0 = a.W2[j], w1 = a.W2[HP + j];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float h = fmaxf(acc[rb][u][g] + bj, 0.f);
-          op[rb][g][0] = fmaf(h, w0, op[rb][g][0]);
-          op[rb][g][1] = fmaf(h, w1, op[rb][g][1]);
-        }
-    }
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-          op[rb][g][0] += __shfl_xor(op[rb][g][0], o);
-          op[rb][g][1] += __shfl_xor(op[rb][g][1], o);
-        }
-      }
-    if (lr == 0) {
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          red[w][16 * rb + 4 * lq + g][0] = op[rb][g][0];
-          red[w][16 * rb + 4 * lq + g][1] = op[rb][g][1];
-        }
-    }
+    out_partials<2, RB, NT>(acc, a.b1, 0, a.W2, 0, HP, w, lr, lq, &red[0][0][0]);
     __syncthreads();
     if (tid < RT && row0 + tid < a.n) {
       const int r = tid;
       const long long row = row0 + r;
-      const float l0 = (((red[0][r][0] + red[1][r][0]) + red[2][r][0]) + red[3][r][0]) + a.b2[0];
-      const float l1 = (((red[0][r][1] + red[1][r][1]) + red[2][r][1]) + red[3][r][1]) + a.b2[1];
+      const float l0 = out_sum<2, RB>(&red[0][0][0], r, 0) + a.b2[0];
+      const float l1 = out_sum<2, RB>(&red[0][0][0], r, 1) + a.b2[1];
       // scipy.stats.entropy(sigmoid(l)) in float32: pk / sum(pk), then the sum of entr
       const float p0 = 1.f / (1.f + expf(-l0)), p1 = 1.f / (1.f + expf(-l1));
       const float sp = p0 + p1;
@@ -219,15 +196,14 @@ struct MarchArgs {
 };
 
 // The RMSE march (AL/triplependulum_al.py:204-227, :396-420), one ray per workgroup: cls.hip's k_boundary at RT = 64
-// points per round under the wide classifier.  Thread r < RT forms point base + r + 1 by r + 1 sequential float64
-// subtractions from the round's base velocity (the reference's own accumulation) and writes its normalised float32
-// inputs to the staging tile `xs`; the tile body is k_fwd's, statement by statement, with its A rows read from that
-// tile, so a point's label is what k_fwd gives the same float32 row (same k order, same two-logit reduction).  The
-// ray's float64 state lives in LDS across the body.  The first point whose label differs from the start label, whose
+// points per round under the wide classifier, with the same ray helpers (nn_common.h).  Thread r < RT forms point
+// base + r + 1 from the round's base velocity and writes its normalised float32 inputs to the staging tile `xs`; the
+// tile body is k_fwd's own (tile_gemm, out_partials) with its A rows read from that tile, so a point's label is what
+// k_fwd gives the same float32 row.  The ray's float64 state lives in LDS across the body.  The first point whose label differs from the start label, whose
 // stop norm is not > 1e-2 or whose index is max_steps ends the ray; rounds = ceil(max_steps / RT) is known at launch.
 template <int NIN, int NT>
 __global__ __launch_bounds__(256) void k_march(MarchArgs a) {
-  constexpr int HP = 64 * NT, TG = HP / 16, ST = stride0(NIN), NQ = NIN / 2;
+  constexpr int HP = 64 * NT, ST = stride0(NIN), NQ = NIN / 2;
   __shared__ __attribute__((aligned(16))) float w0s[HP * ST];
   __shared__ float red[4][RT][2];
   __shared__ float xs[RT][NIN];         // the round's points, normalised
@@ -245,14 +221,8 @@ __global__ __launch_bounds__(256) void k_march(MarchArgs a) {
     double v0[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) v0[i] = xr[NQ + i];
-    double s2 = v0[0] * v0[0], p2 = v0[0] * v0[0];
-#pragma unroll
-    for (int i = 1; i < NQ; ++i) {
-      s2 += v0[i] * v0[i];
-      if (i < a.od) p2 += v0[i] * v0[i];
-    }
-    const double vel_norm = sqrt(s2);
-    const double sn = partial ? sqrt(p2) : vel_norm;
+    double sn;
+    const double vel_norm = ray_norm<NQ, false>(v0, a.od, partial, sn);
     if (!(sn > 1e-2)) {     // no step taken; every thread of the workgroup sees the same values
       if (tid == 0) {
         a.err[ray] = 0.0;
@@ -261,11 +231,10 @@ __global__ __launch_bounds__(256) void k_march(MarchArgs a) {
       }
       return;
     }
-    // `v0 - 1e-2 * X_test[i][3] / vel_norm`: (1e-2 * x) / vel_norm, subtracted for label 0 and added for label 1
     if (tid < NQ) {
       const double vt = xr[NQ + tid];
       vb[tid] = vt;
-      cst[tid] = (label ? -1.0 : 1.0) * ((1e-2 * vt) / vel_norm);
+      cst[tid] = ray_step(vt, vel_norm, label);
     }
     if (tid == 0) vn0 = vel_norm;
   }
@@ -285,21 +254,11 @@ __global__ __launch_bounds__(256) void k_march(MarchArgs a) {
         v[i] = vb[i];
         c[i] = cst[i];
       }
-      for (int k = 0; k <= tid; ++k) {
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) v[i] = v[i] - c[i];
-      }
-      double q2 = v[0] * v[0], p2 = v[0] * v[0];
-#pragma unroll
-      for (int i = 1; i < NQ; ++i) {
-        q2 += v[i] * v[i];
-        if (i < a.od) p2 += v[i] * v[i];
-      }
+      ray_point<NQ>(v, c, tid);
 #pragma unroll
       for (int i = 0; i < NQ; ++i) xs[tid][NQ + i] = ((float)v[i] - a.mean) / a.std;
-      const double vn = sqrt(q2);
-      const double sn = partial ? sqrt(p2) : vn;
-      vnl[tid] = vn;
+      double sn;
+      vnl[tid] = ray_norm<NQ, false>(v, a.od, partial, sn);
       stopl[tid] = ((!(sn > 1e-2)) << 1) | ((base + tid + 1 >= a.max_steps) << 2);
       if (tid == RT - 1) {
 #pragma unroll
@@ -308,101 +267,21 @@ __global__ __launch_bounds__(256) void k_march(MarchArgs a) {
     }
     __syncthreads();
 
-    // ---- k_fwd's tile body over the staging tile ----
+    // k_fwd's tile body over the staging tile (no float64 value is live across it)
     float x[RB][NIN];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int i = 0; i < NIN; ++i) x[rb][i] = xs[16 * rb + lr][i];
     f4 acc[RB][NT];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int u = 0; u < NT; ++u) acc[rb][u] = f4{0.f, 0.f, 0.f, 0.f};
-    const float* bp = a.Wf + ((size_t)w * TG * 64 + lane) * 4;
-
-    auto group = [&](int t, const f4 (&bv)[NT]) {
-      const float* wk = w0s + (16 * t + 4 * lq) * ST;
-      float av[RB][4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float wc[NIN];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) wc[i] = wk[s * ST + i];
-        const float bc = wk[s * ST + NIN];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          float sum = 0.f;
-#pragma unroll
-          for (int i = 0; i < NIN; ++i) sum = fmaf(x[rb][i], wc[i], sum);
-          av[rb][s] = fmaxf(sum + bc, 0.f);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int u = 0; u < NT; ++u) acc[rb][u] = mfma(av[rb][s], bv[u][s], acc[rb][u]);
-    };
-
-    f4 b0[NT], b1[NT];
-#pragma unroll
-    for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256);
-    for (int t = 0; t < TG; t += 2) {
-#pragma unroll
-      for (int u = 0; u < NT; ++u) b1[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 1));
-      group(t, b0);
-      if (t + 2 < TG) {
-#pragma unroll
-        for (int u = 0; u < NT; ++u) b0[u] = *(const f4*)(bp + (size_t)u * 4 * TG * 256 + 256 * (t + 2));
-      }
-      group(t + 1, b1);
-    }
-
-    float op[RB][4][2];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) op[rb][g][0] = op[rb][g][1] = 0.f;
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      const int j = 16 * (w + 4 * u) + lr;
-      const float bj = a.b1[j], w0 = a.W2[j], w1 = a.W2[HP + j];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float h = fmaxf(acc[rb][u][g] + bj, 0.f);
-          op[rb][g][0] = fmaf(h, w0, op[rb][g][0]);
-          op[rb][g][1] = fmaf(h, w1, op[rb][g][1]);
-        }
-    }
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-          op[rb][g][0] += __shfl_xor(op[rb][g][0], o);
-          op[rb][g][1] += __shfl_xor(op[rb][g][1], o);
-        }
-      }
-    if (lr == 0) {
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          red[w][16 * rb + 4 * lq + g][0] = op[rb][g][0];
-          red[w][16 * rb + 4 * lq + g][1] = op[rb][g][1];
-        }
-    }
+    tile_gemm<NIN, NT>(x, w0s, a.Wf, w, lane, lq, acc);
+    out_partials<2, RB, NT>(acc, a.b1, 0, a.W2, 0, HP, w, lr, lq, &red[0][0][0]);
     __syncthreads();
-    // ---- the march's epilogue: wave 0 holds the round's RT points, one per lane ----
+    // the march's epilogue: wave 0 holds the round's RT points, one per lane
     if (tid < RT) {
       const int r = tid;
-      const float l0 = (((red[0][r][0] + red[1][r][0]) + red[2][r][0]) + red[3][r][0]) + a.b2[0];
-      const float l1 = (((red[0][r][1] + red[1][r][1]) + red[2][r][1]) + red[3][r][1]) + a.b2[1];
+      const float l0 = out_sum<2, RB>(&red[0][0][0], r, 0) + a.b2[0];
+      const float l1 = out_sum<2, RB>(&red[0][0][0], r, 1) + a.b2[1];
       const int sb = stopl[r] | ((int)(l1 > l0) != label);
       const unsigned long long any = __ballot(sb != 0);
       const int first = any ? __ffsll((long long)any) - 1 : RT;
