@@ -7,7 +7,10 @@
  *   HJR/triplependulum_hjr.py:150-176            the RMSE march along each held-out state's velocity direction
  *   my_nn.py:4-18                                NeuralNetCLS (Linear-ReLU-Linear-ReLU-Linear, two logits)
  * Supported: inputs 2, 4 or 6, hidden 65..128 (padded to 128), minibatch a multiple of 32 up to 4096 (triple and
- * double 100 / 4096, pendulum 100 / 64).  Other shapes return VBOC_CLS_EUNSUPPORTED.
+ * double 100 / 4096, pendulum 100 / 64).  The fit alone (create, set / get_params, train, sample) also at inputs 4 with
+ * hidden 257..320 (padded to 320: the AL double's 300) and inputs 6 with hidden 449..512 (padded to 512: the AL
+ * triple's 500); on such a handle vboc_cls_eval and vboc_cls_boundary return VBOC_CLS_EUNSUPPORTED and write nothing
+ * (the AL loop classifies and marches through vboc_pool.h).  Other shapes return VBOC_CLS_EUNSUPPORTED.
  */
 #ifndef VBOC_CLS_H
 #define VBOC_CLS_H
@@ -59,6 +62,13 @@ int vboc_cls_train(vboc_cls_handle h, const vboc_cls_run_t* run, void* stream);
 /* `steps` minibatch index draws of the sampler (test hook: the same kernel as the fit; advances the stream) into
  * idx_out (device int32 [steps][minibatch]). */
 int vboc_cls_sample(vboc_cls_handle h, long long n, int steps, int* idx_out, void* stream);
+
+/* The same two with a split minibatch (AL/doublependulum_al.py:301-307): with n_new > 0 the last n_new of the n rows
+ * are the new ones, and each minibatch is minibatch/2 distinct old rows, then minibatch/2 distinct new rows.
+ * n_new = 0 is vboc_cls_train / vboc_cls_sample exactly.  n_new < 0, n_new > n, n_new < minibatch/2 and
+ * n - n_new < minibatch/2 (where random.sample would raise) return VBOC_CLS_EARG before anything is queued. */
+int vboc_cls_train_split(vboc_cls_handle h, const vboc_cls_run_t* run, long long n_new, void* stream);
+int vboc_cls_sample_split(vboc_cls_handle h, long long n, long long n_new, int steps, int* idx_out, void* stream);
 
 /* Forward pass over n device rows X [n][ld] (normalised float32 inputs): labels (device uint8 [n]) = argmax of the
  * two logits (a tie gives 0, as np.argmax), logits (device float32 [n][2], optional), *count1 (host) = the number of

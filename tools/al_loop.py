@@ -8,6 +8,7 @@ operations, the pool size and the entropy pass's rate against the FP32 matrix pe
 reference's arithmetic).
 --march device | torch picks the RMSE march: the scorer's kernel (vboc_pool_boundary) or march_reference on the torch
 module (the comparator); auto is al_run's default.  With it the file name gains _march_<device|torch>.
+--native-fit fits the classifier on the device library (al_run(native_fit=True)); the file name gains _native_fit.
 usage: python tools/al_loop.py --nq 3 --iters 1 --fit-steps 200 --out profiles
 """
 import argparse
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--test", type=int, default=100, help="held-out rays of the RMSE march (0: no march)")
     ap.add_argument("--torch", action="store_true", help="pool operations on the torch / NumPy path")
     ap.add_argument("--march", choices=("auto", "device", "torch"), default="auto", help="the RMSE march's path")
+    ap.add_argument("--native-fit", action="store_true", help="the classifier's fits on csrc/cls.hip")
     ap.add_argument("--B", type=int, default=None)
     ap.add_argument("--pool", type=int, default=None, help="pool rows (default: the reference's gridp ** (2 nq))")
     ap.add_argument("--device", default="cuda")
@@ -52,7 +54,7 @@ def main():
     t = time.time()
     r = al_run(a.nq, X_test, pool=pool, B=a.B, N_init=a.B, max_iterations=a.iters, device=a.device,
                native=not a.torch, fit_steps=a.fit_steps,
-               device_march={"auto": None, "device": True, "torch": False}[a.march])
+               device_march={"auto": None, "device": True, "torch": False}[a.march], native_fit=a.native_fit)
     wall = time.time() - t
     s, calls = r["split"], r["scorer"].calls
     B = a.B or c["B"]
@@ -62,6 +64,8 @@ def main():
     flop = 2.0 * n0 * (2 * a.nq * hidden + hidden * hidden + 2 * hidden)     # the first pass's rows, real widths
     out = dict(phase="al", nq=a.nq, scorer="torch" if a.torch else "device", B=B, pool_rows_first_pass=n0,
                hidden=hidden, iterations=r["iterations"], fit_steps_cap=a.fit_steps, wall_s=round(wall, 2),
+               native_fit=r["native_fit"], fit_cls_s=round(s["fit_cls"], 4), fit_cls_steps=s["fit_cls_steps"],
+               fit_cls_ms_per_step=round(1e3 * s["fit_cls"] / max(s["fit_cls_steps"], 1), 4),
                split={k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items()},
                entropy_call_s=[round(x, 5) for x in ent], select_call_s=[round(x, 5) for x in calls["select"]],
                guess_call_s=[round(x, 5) for x in calls["guess"]],
@@ -73,10 +77,12 @@ def main():
                rmse=[float(x) for x in r["rmse"]], times=[round(float(x), 3) for x in r["times"]],
                pool_rows_left=r["pool_rows"])
     print(json.dumps(out), flush=True)
+    print(f"fit_cls {out['fit_cls_s']} s, {out['fit_cls_steps']} steps, {out['fit_cls_ms_per_step']} ms per step "
+          f"({'native' if r['native_fit'] else 'torch'})", file=sys.stderr, flush=True)
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         name = f"al_loop_{'triple' if a.nq == 3 else 'double'}_{'torch' if a.torch else 'device'}" \
-               f"{'' if a.march == 'auto' else '_march_' + a.march}.json"
+               f"{'' if a.march == 'auto' else '_march_' + a.march}{'_native_fit' if a.native_fit else ''}.json"
         with open(os.path.join(a.out, name), "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")

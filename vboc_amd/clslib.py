@@ -12,7 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvboc_cls.so")
 SRC = os.path.join(HERE, "csrc", "cls.hip")
 EXPORTS = ("vboc_cls_create", "vboc_cls_destroy", "vboc_cls_set_params", "vboc_cls_get_params", "vboc_cls_train",
-           "vboc_cls_sample", "vboc_cls_eval", "vboc_cls_boundary", "vboc_cls_last_error")
+           "vboc_cls_sample", "vboc_cls_train_split", "vboc_cls_sample_split", "vboc_cls_eval", "vboc_cls_boundary",
+           "vboc_cls_last_error")
 EUNSUPPORTED = -3
 
 
@@ -57,6 +58,8 @@ def load():
     lib.vboc_cls_get_params.argtypes = [vp, ctypes.c_int] + [vp] * 7
     lib.vboc_cls_train.argtypes = [vp, ctypes.POINTER(ClsRun), vp]
     lib.vboc_cls_sample.argtypes = [vp, ll, ctypes.c_int, vp, vp]
+    lib.vboc_cls_train_split.argtypes = [vp, ctypes.POINTER(ClsRun), ll, vp]
+    lib.vboc_cls_sample_split.argtypes = [vp, ll, ll, ctypes.c_int, vp, vp]
     lib.vboc_cls_eval.argtypes = [vp, vp, ll, ctypes.c_int, vp, vp, ctypes.POINTER(ll), vp]
     lib.vboc_cls_boundary.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_int, vp, vp, vp, vp]
@@ -71,3 +74,10 @@ def check(rc):
 
 def supported(inputs, hidden, minibatch):
     return inputs in (2, 4, 6) and 65 <= hidden <= 128 and minibatch % 32 == 0 and 32 <= minibatch <= 4096
+
+
+def fit_supported(inputs, hidden, minibatch):
+    """The shapes the training step exists at: `supported`'s, and fit.hip's wide ones (the AL loop's 300 and 500),
+    where the handle is a trainer only."""
+    wide = (inputs == 4 and 257 <= hidden <= 320) or (inputs == 6 and 449 <= hidden <= 512)
+    return supported(inputs, hidden, minibatch) or (wide and minibatch % 32 == 0 and 32 <= minibatch <= 4096)

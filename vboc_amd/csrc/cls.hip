@@ -1,6 +1,9 @@
 // The classifier of the HJR (and AL) loops on the device: Adam / BCEWithLogitsLoss training of NeuralNetCLS
-// (Linear-ReLU-Linear-ReLU-Linear, two logits, hidden <= 128) with the reference's minibatch sampling and stop rule,
-// the classification of a candidate set, and the RMSE march along each held-out state's velocity direction.
+// (Linear-ReLU-Linear-ReLU-Linear, two logits) with the reference's minibatch sampling and stop rule, the
+// classification of a candidate set, and the RMSE march along each held-out state's velocity direction.  The training
+// kernels are templates over <inputs, padded hidden> and exist at hidden 128 (HJR: inputs 2, 4, 6) and, as fit.hip's,
+// at (4, 320) and (6, 512) (the AL loop's 300 and 500); the forward-only kernels exist at 128 alone (the AL loop
+// classifies and marches on pool.hip).
 //
 // Reference: HJR/triplependulum_hjr.py:95-118 and :234-258 (random.sample(range(n), 4096), BCEWithLogitsLoss,
 // Adam(lr 1e-3), val = beta val + (1 - beta) loss from val = 1, `while val > loss_stop and it < it_max`), :136-148
@@ -30,10 +33,8 @@
 
 namespace {
 
-constexpr int HP = 128;       // padded hidden size
+constexpr int HPF = 128;      // padded hidden size of the forward-only kernels (k_eval, k_boundary)
 constexpr int R2 = 16;        // rows per workgroup and round
-constexpr int NT = HP / 64;   // 16-column tiles per wave
-constexpr int LD = HP + 4;    // LDS row stride of the activations
 constexpr int EVG = 2048;     // most workgroups (= partial counts) of one evaluation
 constexpr int MAX_STEPS = 16384;
 
@@ -58,12 +59,12 @@ struct Args {
   float* dW1p;                // split partials of dW1 [S][HP][HP]
   State* st;
   const float* F;             // rows [n][ldF]: NIN normalised inputs then the two targets
-  long long n, n_new;         // n_new is always 0 (one row range)
+  long long n, n_new;         // n_new > 0: the last n_new rows are the new ones (half of each minibatch from them)
   int ldF, Bt, S;
   float lr;
 };
 
-template <int NIN>
+template <int NIN, int HP>
 struct Lay {
   static constexpr int W0 = 0, B0 = HP * NIN, B1 = B0 + HP, W2 = B1 + HP, B2 = W2 + 2 * HP, SMALL = B2 + 4;
   static constexpr int W1 = SMALL, TOTAL = W1 + HP * HP, REC = SMALL + 4, LOSS = SMALL;
@@ -75,9 +76,11 @@ __global__ __launch_bounds__(SNT) void k_sample(Args a) {
   sample_minibatch(L, a, a.idx);
 }
 
-template <int NIN>
+template <int NIN, int HP>
 __global__ __launch_bounds__(256) void k_fwd_bwd(Args a) {
-  using Ly = Lay<NIN>;
+  using Ly = Lay<NIN, HP>;
+  constexpr int NT = HP / 64;          // 16-column tiles per wave
+  constexpr int LD = HP + 4;           // LDS row stride of the activations
   struct FwdLds {
     float H1[R2 * LD];
     float G2[R2 * LD];
@@ -220,9 +223,9 @@ __global__ __launch_bounds__(256) void k_fwd_bwd(Args a) {
 
 // dW1 partials: workgroup = 64 x 64 output block x one of S row splits; wave = 32 x 32 (2 x 2 MFMA tiles).
 // Block 0's first wave also applies the reference's loop update: val = beta val + (1 - beta) loss, it += 1.
-template <int NIN>
+template <int NIN, int HP>
 __global__ __launch_bounds__(256) void k_dw1(Args a) {
-  using Ly = Lay<NIN>;
+  using Ly = Lay<NIN, HP>;
   State* st = a.st;
   if (!st->gate) return;
   constexpr int NB = HP / 64;
@@ -276,9 +279,9 @@ __global__ __launch_bounds__(256) void k_dw1(Args a) {
   }
 }
 
-template <int NIN>
+template <int NIN, int HP>
 __global__ __launch_bounds__(256) void k_adam(Args a) {
-  using Ly = Lay<NIN>;
+  using Ly = Lay<NIN, HP>;
   __shared__ float tile[32][33];
   __shared__ float red[16][17];
   const State* st = a.st;
@@ -336,10 +339,10 @@ __global__ __launch_bounds__(256) void k_adam(Args a) {
 }
 
 // torch layouts <-> padded buffers (H real hidden units)
-template <int NIN>
+template <int NIN, int HP>
 __global__ void k_pack(float* P, float* Wf, float* Wb, float* W0, float* b0, float* W1, float* b1, float* W2,
                        float* b2, int H, int unpack) {
-  using Ly = Lay<NIN>;
+  using Ly = Lay<NIN, HP>;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < HP * HP) {
     const int j = i / HP, c = i % HP;
@@ -380,7 +383,7 @@ __global__ void k_pack(float* P, float* Wf, float* Wb, float* W0, float* b0, flo
 // the forward pass alone: classification and the march
 // ------------------------------------------------------------------------------------------------
 struct FwdOnlyLds {
-  float H1[R2 * LD];
+  float H1[R2 * (HPF + 4)];
   float xs[R2 * 6];
   float red[4][R2][2];
   float lg[R2][2];
@@ -390,10 +393,10 @@ struct FwdOnlyLds {
 // L.lg, through the training forward's own code (forward_rows).  Called by all 256 threads; ends on a barrier.
 template <int NIN>
 __device__ __forceinline__ void forward16(const float* P, const float* Wf, FwdOnlyLds& L) {
-  using Ly = Lay<NIN>;
+  using Ly = Lay<NIN, HPF>;
   const int tid = threadIdx.x;
-  f4 acc[NT];
-  forward_rows<NIN, HP, 2, Ly>(P, Wf, L.xs, L.H1, &L.red[0][0][0], acc);
+  f4 acc[HPF / 64];
+  forward_rows<NIN, HPF, 2, Ly>(P, Wf, L.xs, L.H1, &L.red[0][0][0], acc);
   __syncthreads();
   if (tid < 2 * R2) {
     const int r = tid >> 1, o = tid & 1;
@@ -556,7 +559,7 @@ __global__ __launch_bounds__(256) void k_boundary(MarchArgs a) {
 // host side
 // ------------------------------------------------------------------------------------------------
 struct vboc_cls {
-  int nin, hidden, bt, S;
+  int nin, hidden, hp, bt, S;
   int total, rec;
   float *P = nullptr, *M = nullptr, *V = nullptr, *Wf = nullptr, *Wb = nullptr;
   float *H1p = nullptr, *dH2p = nullptr, *part = nullptr, *dW1p = nullptr;
@@ -583,13 +586,27 @@ static int cfail(int code, const std::string& m) {
     if (e_ != hipSuccess) return cfail(VBOC_CLS_EHIP, std::string(#x ": ") + hipGetErrorString(e_)); \
   } while (0)
 
-template <int NIN>
+// The handle's instantiation <inputs, padded hidden>, as a tag: (2 | 4 | 6, 128), (4, 320) or (6, 512).
+template <int NIN_, int HP_>
+struct Shape {
+  static constexpr int NIN = NIN_, HP = HP_;
+};
+template <class F>
+static void with_shape(const vboc_cls* h, F&& f) {
+  if (h->hp == 512) f(Shape<6, 512>{});
+  else if (h->hp == 320) f(Shape<4, 320>{});
+  else if (h->nin == 6) f(Shape<6, 128>{});
+  else if (h->nin == 4) f(Shape<4, 128>{});
+  else f(Shape<2, 128>{});
+}
+
+template <int NIN, int HP>
 static void launch_train(const vboc_cls* h, const Args& a, hipStream_t s) {
   constexpr int NW1 = (HP / 32) * (HP / 32);
-  const int nsmall = (Lay<NIN>::SMALL + 15) / 16;
-  hipLaunchKernelGGL((k_fwd_bwd<NIN>), dim3(h->bt / R2 + 1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL((k_dw1<NIN>), dim3((HP / 64) * (HP / 64) * h->S), dim3(256), 0, s, a);
-  hipLaunchKernelGGL((k_adam<NIN>), dim3(NW1 + nsmall), dim3(256), 0, s, a);
+  const int nsmall = (Lay<NIN, HP>::SMALL + 15) / 16;
+  hipLaunchKernelGGL((k_fwd_bwd<NIN, HP>), dim3(h->bt / R2 + 1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((k_dw1<NIN, HP>), dim3((HP / 64) * (HP / 64) * h->S), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((k_adam<NIN, HP>), dim3(NW1 + nsmall), dim3(256), 0, s, a);
 }
 
 // Step i of a chunk uses the minibatch in idx[(parity + i) % 2], drawn by the previous step's forward kernel
@@ -599,19 +616,30 @@ static void chunk(const vboc_cls* h, const Args& base, int steps, int parity, hi
     Args a = base;
     a.idx = h->idx[(parity + i) & 1];
     a.idx_next = h->idx[(parity + i + 1) & 1];
-    if (h->nin == 6) launch_train<6>(h, a, s);
-    else if (h->nin == 4) launch_train<4>(h, a, s);
-    else launch_train<2>(h, a, s);
+    with_shape(h, [&](auto sh) { launch_train<decltype(sh)::NIN, decltype(sh)::HP>(h, a, s); });
   }
+}
+
+template <int NIN, int HP>
+static void pack(vboc_cls* h, float* W0, float* b0, float* W1, float* b1, float* W2, float* b2, int unpack,
+                 float* src) {
+  hipLaunchKernelGGL((k_pack<NIN, HP>), dim3((HP * HP + 255) / 256), dim3(256), 0, h->stream, src, h->Wf, h->Wb, W0,
+                     b0, W1, b1, W2, b2, h->hidden, unpack);
 }
 
 static void pack(vboc_cls* h, float* W0, float* b0, float* W1, float* b1, float* W2, float* b2, int unpack,
                  float* src) {
-  dim3 g((HP * HP + 255) / 256), b(256);
-  float *Wf = h->Wf, *Wb = h->Wb;
-  if (h->nin == 6) hipLaunchKernelGGL((k_pack<6>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
-  else if (h->nin == 4) hipLaunchKernelGGL((k_pack<4>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
-  else hipLaunchKernelGGL((k_pack<2>), g, b, 0, h->stream, src, Wf, Wb, W0, b0, W1, b1, W2, b2, h->hidden, unpack);
+  with_shape(h, [&](auto sh) { pack<decltype(sh)::NIN, decltype(sh)::HP>(h, W0, b0, W1, b1, W2, b2, unpack, src); });
+}
+
+// a refit's row ranges: n_new = 0 is one range; else each half of the minibatch needs its range to hold it
+static int check_rows(const vboc_cls* h, long long n, long long n_new) {
+  if (n_new < 0 || n_new > n) return cfail(VBOC_CLS_EARG, "n_new outside [0, n]");
+  if (n_new == 0 && n < h->bt) return cfail(VBOC_CLS_EARG, "fewer rows than one minibatch");
+  if (n_new != 0 && (n_new < h->bt / 2 || n - n_new < h->bt / 2))
+    return cfail(VBOC_CLS_EARG, "a split minibatch needs at least minibatch/2 old and minibatch/2 new rows");
+  if (n >= (1ll << 31)) return cfail(VBOC_CLS_EARG, "more than 2^31 rows");
+  return 0;
 }
 
 // the caller's stream waits for the classifier's, or the other way round
@@ -628,22 +656,28 @@ const char* vboc_cls_last_error(void) { return g_cls_err.c_str(); }
 int vboc_cls_create(int nin, int hidden, int minibatch, unsigned long long seed, vboc_cls_handle* out) {
   if (!out) return cfail(VBOC_CLS_EARG, "out is null");
   *out = nullptr;
-  if ((nin != 2 && nin != 4 && nin != 6) || hidden < 65 || hidden > HP)
-    return cfail(VBOC_CLS_EUNSUPPORTED, "native classifier supports inputs 2, 4, 6 and hidden 65..128");
+  const int hp = (hidden + 63) / 64 * 64;
+  const bool narrow = (nin == 2 || nin == 4 || nin == 6) && hidden >= 65 && hidden <= 128;
+  if (!narrow && !(nin == 4 && hp == 320) && !(nin == 6 && hp == 512))
+    return cfail(VBOC_CLS_EUNSUPPORTED, "native classifier supports inputs 2, 4, 6 with hidden 65..128, and the fit "
+                                        "alone at (inputs, hidden) = (4, 257..320) and (6, 449..512)");
   if (minibatch < 32 || minibatch % 32 || minibatch > MAXK)
     return cfail(VBOC_CLS_EUNSUPPORTED, "minibatch must be a multiple of 32 in [32, 4096]");
   vboc_cls* h = new vboc_cls();
   h->nin = nin;
   h->hidden = hidden;
+  h->hp = hp;
   h->bt = minibatch;
   // split of the dW1 rows: about 256 workgroups, each split a multiple of 32 rows
-  const int blocks = (HP / 64) * (HP / 64);
+  const int blocks = (hp / 64) * (hp / 64);
   int S = 1;
   while (blocks * S * 2 <= 256 && (minibatch / (S * 2)) % 32 == 0) S *= 2;
   h->S = S;
-  if (nin == 6) { h->total = Lay<6>::TOTAL; h->rec = Lay<6>::REC; }
-  else if (nin == 4) { h->total = Lay<4>::TOTAL; h->rec = Lay<4>::REC; }
-  else { h->total = Lay<2>::TOTAL; h->rec = Lay<2>::REC; }
+  with_shape(h, [&](auto sh) {
+    using Ly = Lay<decltype(sh)::NIN, decltype(sh)::HP>;
+    h->total = Ly::TOTAL;
+    h->rec = Ly::REC;
+  });
   auto fail_free = [&](hipError_t e, const char* what) {
     vboc_cls_destroy(h);
     return cfail(VBOC_CLS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -654,14 +688,14 @@ int vboc_cls_create(int nin, int hidden, int minibatch, unsigned long long seed,
   CALLOC(h->P, sizeof(float) * h->total);
   CALLOC(h->M, sizeof(float) * h->total);
   CALLOC(h->V, sizeof(float) * h->total);
-  CALLOC(h->Wf, sizeof(float) * HP * HP);
-  CALLOC(h->Wb, sizeof(float) * HP * HP);
+  CALLOC(h->Wf, sizeof(float) * hp * hp);
+  CALLOC(h->Wb, sizeof(float) * hp * hp);
   CALLOC(h->idx[0], sizeof(int) * minibatch);
   CALLOC(h->idx[1], sizeof(int) * minibatch);
-  CALLOC(h->H1p, sizeof(float) * (size_t)HP * minibatch);
-  CALLOC(h->dH2p, sizeof(float) * (size_t)HP * minibatch);
+  CALLOC(h->H1p, sizeof(float) * (size_t)hp * minibatch);
+  CALLOC(h->dH2p, sizeof(float) * (size_t)hp * minibatch);
   CALLOC(h->part, sizeof(float) * (size_t)(minibatch / R2) * h->rec);
-  CALLOC(h->dW1p, sizeof(float) * (size_t)S * HP * HP);
+  CALLOC(h->dW1p, sizeof(float) * (size_t)S * hp * hp);
   CALLOC(h->st, sizeof(State));
   CALLOC(h->epart, sizeof(int) * EVG);
   CALLOC(h->etotal, sizeof(long long));
@@ -675,8 +709,8 @@ int vboc_cls_create(int nin, int hidden, int minibatch, unsigned long long seed,
   (void)hipMemsetAsync(h->P, 0, sizeof(float) * h->total, h->stream);
   (void)hipMemsetAsync(h->M, 0, sizeof(float) * h->total, h->stream);
   (void)hipMemsetAsync(h->V, 0, sizeof(float) * h->total, h->stream);
-  (void)hipMemsetAsync(h->Wf, 0, sizeof(float) * HP * HP, h->stream);
-  (void)hipMemsetAsync(h->Wb, 0, sizeof(float) * HP * HP, h->stream);
+  (void)hipMemsetAsync(h->Wf, 0, sizeof(float) * hp * hp, h->stream);
+  (void)hipMemsetAsync(h->Wb, 0, sizeof(float) * hp * hp, h->stream);
   State s{};
   s.seed = seed;
   *h->st_host = s;
@@ -725,10 +759,13 @@ int vboc_cls_get_params(vboc_cls_handle h, int which, float* W0, float* b0, floa
 }
 
 int vboc_cls_train(vboc_cls_handle h, const vboc_cls_run_t* r, void* stream) {
+  return vboc_cls_train_split(h, r, 0, stream);
+}
+
+int vboc_cls_train_split(vboc_cls_handle h, const vboc_cls_run_t* r, long long n_new, void* stream) {
   if (!h || !r || !r->F) return cfail(VBOC_CLS_EARG, "null argument");
   if (r->ld < h->nin + 2) return cfail(VBOC_CLS_EARG, "ld < inputs + 2");
-  if (r->n < h->bt) return cfail(VBOC_CLS_EARG, "fewer rows than one minibatch");
-  if (r->n >= (1ll << 31)) return cfail(VBOC_CLS_EARG, "more than 2^31 rows");
+  if (int rc = check_rows(h, r->n, n_new)) return rc;
   if (r->it_max < 1) return cfail(VBOC_CLS_EARG, "it_max < 1");
   // a graph replays an even number of steps, so every replay starts on idx[0]
   const int poll = r->graphs ? (r->poll > 2 ? (r->poll + 1) / 2 * 2 : 2) : (r->poll > 0 ? r->poll : 1);
@@ -736,7 +773,7 @@ int vboc_cls_train(vboc_cls_handle h, const vboc_cls_run_t* r, void* stream) {
   memset(&a, 0, sizeof a);
   a.P = h->P; a.M = h->M; a.V = h->V; a.Wf = h->Wf; a.Wb = h->Wb; a.idx = nullptr;
   a.H1p = h->H1p; a.dH2p = h->dH2p; a.part = h->part; a.dW1p = h->dW1p; a.st = h->st;
-  a.F = r->F; a.n = r->n; a.n_new = 0; a.ldF = r->ld; a.Bt = h->bt; a.S = h->S; a.lr = (float)r->lr;
+  a.F = r->F; a.n = r->n; a.n_new = n_new; a.ldF = r->ld; a.Bt = h->bt; a.S = h->S; a.lr = (float)r->lr;
   // loop state of the reference: it = 0, val = 1
   CCHK(hipStreamSynchronize(h->stream));
   State* s = h->st_host;
@@ -803,14 +840,17 @@ int vboc_cls_train(vboc_cls_handle h, const vboc_cls_run_t* r, void* stream) {
 }
 
 int vboc_cls_sample(vboc_cls_handle h, long long n, int steps, int* idx_out, void* stream) {
+  return vboc_cls_sample_split(h, n, 0, steps, idx_out, stream);
+}
+
+int vboc_cls_sample_split(vboc_cls_handle h, long long n, long long n_new, int steps, int* idx_out, void* stream) {
   if (!h || !idx_out || steps < 0) return cfail(VBOC_CLS_EARG, "bad argument");
-  if (n < h->bt) return cfail(VBOC_CLS_EARG, "fewer rows than one minibatch");
-  if (n >= (1ll << 31)) return cfail(VBOC_CLS_EARG, "more than 2^31 rows");
+  if (int rc = check_rows(h, n, n_new)) return rc;
   if (int rc = order(h->ev_in, (hipStream_t)stream, h->stream)) return rc;
   Args a;
   memset(&a, 0, sizeof a);
   a.idx = h->idx[0]; a.st = h->st;
-  a.n = n; a.n_new = 0; a.Bt = h->bt; a.S = h->S;
+  a.n = n; a.n_new = n_new; a.Bt = h->bt; a.S = h->S;
   for (int i = 0; i < steps; ++i) {
     hipLaunchKernelGGL(k_sample, dim3(1), dim3(SNT), 0, h->stream, a);
     CCHK(hipGetLastError());
@@ -824,6 +864,7 @@ int vboc_cls_sample(vboc_cls_handle h, long long n, int steps, int* idx_out, voi
 int vboc_cls_eval(vboc_cls_handle h, const float* X, long long n, int ld, unsigned char* labels, float* logits,
                   long long* count1, void* stream) {
   if (!h) return cfail(VBOC_CLS_EARG, "null handle");
+  if (h->hp != HPF) return cfail(VBOC_CLS_EUNSUPPORTED, "a handle with hidden > 128 is a trainer only");
   if (n < 0 || n >= (1ll << 31)) return cfail(VBOC_CLS_EARG, "rows outside [0, 2^31)");
   if (count1) *count1 = 0;
   if (n == 0) return 0;
@@ -849,6 +890,7 @@ int vboc_cls_eval(vboc_cls_handle h, const float* X, long long n, int ld, unsign
 int vboc_cls_boundary(vboc_cls_handle h, const double* X_test, int m, int nq, float mean, float std, int max_steps,
                       double* err, int* steps, unsigned char* flags, void* stream) {
   if (!h) return cfail(VBOC_CLS_EARG, "null handle");
+  if (h->hp != HPF) return cfail(VBOC_CLS_EUNSUPPORTED, "a handle with hidden > 128 is a trainer only");
   if (m < 0) return cfail(VBOC_CLS_EARG, "m < 0");
   if ((nq != 2 && nq != 3) || 2 * nq != h->nin) return cfail(VBOC_CLS_EARG, "the march needs nq 2 or 3 = inputs / 2");
   if (m == 0) return 0;

@@ -588,7 +588,8 @@ class ClsTrainer:
     fit(F, it_max): F [n, 2nq + 2] float32 = normalised inputs, then the two targets.  The minibatch rows come from
     `self.sampler(n, 1)`: by default random.sample of a random.Random(seed), or an injected callable (n, steps) ->
     [steps, k] indices.  predict_labels / boundary_errors run on the device kernels (libvboc_cls.so) when the model
-    is on a GPU and the shape is supported (they are not the NN fit), else on PyTorch."""
+    is on a GPU and the shape is `clslib.supported` (they are not the NN fit), else on PyTorch.  The native handle
+    exists for every `clslib.fit_supported` shape; at hidden > 128 it is a trainer only (HipClsTrainer's)."""
 
     def __init__(self, nq, device="cpu", hidden=100, minibatch=None, lr=1e-3, beta=0.95, stop_val=5e-3, seed=0,
                  sampler=None, native_eval=True, max_steps=CLS_MAX_STEPS):
@@ -609,14 +610,16 @@ class ClsTrainer:
         self.last = None
         self._h = None
         self._cl = None
+        self._fwd = False           # the handle also classifies and marches (hidden <= 128)
         if native_eval and self.device.type == "cuda":
             from . import clslib
-            if clslib.supported(self.nin, hidden, self.k):      # a missing library is an error, not a fall-back
+            if clslib.fit_supported(self.nin, hidden, self.k):  # a missing library is an error, not a fall-back
                 import ctypes
                 self._cl, self._lib = clslib, clslib.load()
                 h = ctypes.c_void_p()
                 clslib.check(self._lib.vboc_cls_create(self.nin, hidden, self.k, seed, ctypes.byref(h)))
                 self._h = h
+                self._fwd = clslib.supported(self.nin, hidden, self.k)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -670,7 +673,7 @@ class ClsTrainer:
         argmax of the two logits, a tie gives 0 (:136-148).  logits=True appends the [n, 2] logits."""
         X = self._rows(X)
         n = X.shape[0]
-        if self._h is not None:
+        if self._fwd:
             import ctypes
             lab = torch.empty((n,), dtype=torch.uint8, device=self.device)
             lg = torch.empty((n, 2), dtype=torch.float32, device=self.device) if logits else None
@@ -694,7 +697,7 @@ class ClsTrainer:
         m = X.shape[0]
         mean_t = torch.as_tensor(mean, dtype=torch.float32).to(self.device)
         std_t = torch.as_tensor(std, dtype=torch.float32).to(self.device)
-        if self._h is not None and self.nq in (2, 3):
+        if self._fwd and self.nq in (2, 3):
             Xd = torch.as_tensor(X).to(self.device)
             err = torch.empty((m,), dtype=torch.float64, device=self.device)
             steps = torch.empty((m,), dtype=torch.int32, device=self.device)
@@ -718,7 +721,10 @@ class HipClsTrainer(ClsTrainer):
     """ClsTrainer's fit on the device kernels of csrc/cls.hip (libvboc_cls.so, include/vboc_cls.h): sampling,
     forward, BCE, backward, Adam and the stop rule in three kernels per step, `poll` steps per HIP graph.  The torch
     module stays the source of truth between fits; Adam's moments and step count live in the native trainer across
-    fits.  The minibatches are the native sampler's (Philox, random.sample's set method); `sample` advances it."""
+    fits.  The minibatches are the native sampler's (Philox, random.sample's set method); `sample` advances it.
+    n_new > 0 (fit and sample) draws half of each minibatch from the first n - n_new rows and half from the last n_new
+    (AL/doublependulum_al.py:301-307).  Shapes: clslib.fit_supported; at hidden > 128 predict_labels and
+    boundary_errors stay on PyTorch."""
 
     def __init__(self, nq, device="cuda", graphs=True, poll=64, **kw):
         super().__init__(nq, device, native_eval=True, **kw)
@@ -726,12 +732,12 @@ class HipClsTrainer(ClsTrainer):
             raise ValueError("HipClsTrainer needs a GPU, libvboc_cls.so and a supported shape")
         self.use_graphs, self.poll = graphs, poll
 
-    def sample(self, n, steps=1):
+    def sample(self, n, steps=1, n_new=0):
         out = torch.empty((steps, self.k), dtype=torch.int32, device=self.device)
-        self._cl.check(self._lib.vboc_cls_sample(self._h, n, steps, out.data_ptr(), self._stream()))
+        self._cl.check(self._lib.vboc_cls_sample_split(self._h, n, n_new, steps, out.data_ptr(), self._stream()))
         return out.cpu().numpy().astype(np.int64)
 
-    def fit(self, F, it_max):
+    def fit(self, F, it_max, n_new=0):
         import ctypes
         F = self._rows(F)
         n = F.shape[0]
@@ -744,7 +750,7 @@ class HipClsTrainer(ClsTrainer):
                               beta=self.beta, lr=self.lr, poll=self.poll, graphs=int(self.use_graphs),
                               iterations=ctypes.addressof(its), val=ctypes.addressof(val),
                               launched=ctypes.addressof(launched), kernel_ms=ctypes.addressof(ms))
-        self._cl.check(self._lib.vboc_cls_train(self._h, ctypes.byref(run), self._stream()))
+        self._cl.check(self._lib.vboc_cls_train_split(self._h, ctypes.byref(run), n_new, self._stream()))
         self._cl.check(self._lib.vboc_cls_get_params(self._h, 0, *ptrs, self._stream()))
         self.total_steps += launched.value
         self.last = dict(iterations=its.value, val=val.value, launched=launched.value, fit_ms=ms.value)
@@ -762,12 +768,12 @@ class HipClsTrainer(ClsTrainer):
 
 def make_cls_trainer(nq, device="cpu", native=False, **kw):
     """The classifier of the HJR loop: ClsTrainer (PyTorch) by default; native=True selects HipClsTrainer on a GPU
-    for the shapes csrc/cls.hip implements (make_trainer's rule).  Either way a GPU run classifies and marches on the
-    device kernels."""
+    for the shapes csrc/cls.hip trains (clslib.fit_supported; make_trainer's rule).  Either way a GPU run at
+    hidden <= 128 classifies and marches on the device kernels."""
     from . import clslib
     dev = torch.device(device)
-    if native and dev.type == "cuda" and clslib.supported(2 * nq, kw.get("hidden", 100),
-                                                          kw.get("minibatch") or CLS_MINIBATCH[nq]):
+    if native and dev.type == "cuda" and clslib.fit_supported(2 * nq, kw.get("hidden", 100),
+                                                              kw.get("minibatch") or CLS_MINIBATCH[nq]):
         return HipClsTrainer(nq, device, **kw)
     return ClsTrainer(nq, device, **kw)
 

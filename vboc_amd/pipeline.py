@@ -735,7 +735,7 @@ def al_default_pool(nq, spec, seed=SEED):
 
 def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=None, minibatch=None, it_max=None,
            max_iterations=None, max_time=None, seed=SEED, device="cuda", out_dir=None, scorer=None, native=None,
-           fit_steps=None, device_march=None):
+           fit_steps=None, device_march=None, native_fit=False):
     """The AL main block for the triple (nq 3) and the double (nq 2) pendulum, statement by statement: the initial
     labels of the pool's first N_init rows (`testing`), the first fits of the classifier and of the guess network,
     then per iteration the entropy of the whole remaining pool, the B most uncertain rows and their removal, their
@@ -749,14 +749,21 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
     from and compacted there, and the guesses go to the solver without visiting the host.  device_march: None runs the
     RMSE march through `scorer.boundary` (vboc_pool_boundary, the classifier's own width) when the scorer is native and
     has one, else through march_reference on the torch module; False always takes the latter; True raises when the
-    scorer cannot march on the device.
+    scorer cannot march on the device.  native_fit=True fits the classifier on csrc/cls.hip (learn.HipClsTrainer) when
+    `device` is a GPU and the shape is clslib.fit_supported (the drivers' 500 and 300 are), else on ClsTrainer as
+    make_trainer's rule does; the torch module stays what the scorer reads, Adam's moments live in the native handle,
+    and the double's refit passes n_new = the rows actually added.  The native classifier draws its minibatches from
+    its own Philox stream: the shared `random.Random` is then consumed only by the guess fit and the double's dead
+    `tkeep` draw, so such a run is not draw-for-draw the transcription (as hjr_run(native=True)).  The guess network's
+    fit is PyTorch either way.
 
     The one deviation: a state whose label is 2 (neither solved nor a QP failure) makes the reference crash
     (`testing` returns None); here it is dropped from the labelled set and counted in `labels[2]`.
 
     Returns dict(times, rmse, etpmax per iteration; capped, march_s: per march the rays stopped by the bound of the
     outward march alone (flags bit 1) and the seconds; queries, scores: the per-iteration row indices into the pool as
-    it stood and their scores; labels: the count of each label; dropped; split: seconds in entropy, select, guess,
+    it stood and their scores; labels: the count of each label; dropped; native_fit: whether the
+    classifier's fits ran on the device library; split: seconds in entropy, select, guess,
     labelling, fit_cls, fit_guess, march; iterations; cls_states, guess_states: both networks' state dicts as they
     stood at each iteration's query; batches: per iteration the queried states, their in-bounds mask and labels;
     trainer, guess_trainer, scorer, mean, std, X_iter, pool, pool_rows) and writes mean_/std_<n>dof_al, times_/rmse_<n>dof_al.npy,
@@ -765,7 +772,8 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
     import random
     import torch
     from . import al as al_mod
-    from .learn import ClsTrainer, GuessTrainer, PoolScorer, march_reference
+    from . import clslib
+    from .learn import ClsTrainer, GuessTrainer, HipClsTrainer, PoolScorer, march_reference
     c = AL[nq]
     B = B or c["B"]
     N_init = N_init or c["N_init"]
@@ -793,8 +801,12 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
                              rng.sample(range(n_old, n), int(n_minibatch / 2)) for _ in range(steps)], dtype=np.int64)
         return np.array([rng.sample(range(n), n_minibatch) for _ in range(steps)], dtype=np.int64)
 
-    tr = ClsTrainer(nq, dev, hidden=hidden, minibatch=n_minibatch, stop_val=AL_LOSS_STOP, seed=seed % (1 << 31),
-                    sampler=cls_sampler, native_eval=False)
+    use_native_fit = bool(native_fit) and dev.type == "cuda" and clslib.fit_supported(2 * nq, hidden, n_minibatch)
+    if use_native_fit:
+        tr = HipClsTrainer(nq, dev, hidden=hidden, minibatch=n_minibatch, stop_val=AL_LOSS_STOP, seed=seed % (1 << 31))
+    else:
+        tr = ClsTrainer(nq, dev, hidden=hidden, minibatch=n_minibatch, stop_val=AL_LOSS_STOP, seed=seed % (1 << 31),
+                        sampler=cls_sampler, native_eval=False)
     gt = GuessTrainer(nq, N, dev, hidden=hidden, stop_val=AL_LOSS_STOP, seed=None, rng=rng)
     if scorer is None:
         scorer = PoolScorer(nq, tr.model, gt.model, dev, native=native)
@@ -859,7 +871,11 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
         Xn = (torch.from_numpy(X_iter[:, :nx].astype(np.float32)).to(dev) - mean) / std
         F = torch.cat([Xn, torch.from_numpy(X_iter[:, nx:].astype(np.float32)).to(dev)], dim=1)
         lim = it_max + 1 if fit_steps is None else min(it_max + 1, fit_steps)      # `it <= it_max`
-        r = timed("fit_cls", lambda: tr.fit(F, lim))
+        if use_native_fit:
+            # the split minibatch is the double's alone (cls_sampler's rule), drawn by the handle's own sampler
+            r = timed("fit_cls", lambda: tr.fit(F, lim, n_new=n_new if nq == 2 else 0))
+        else:
+            r = timed("fit_cls", lambda: tr.fit(F, lim))
         split["fit_cls_steps"] += r["iterations"]
 
     def fit_guess(X_traj, qt):
@@ -949,7 +965,7 @@ def al_run(nq, X_test=None, pool=None, ocp=None, B=None, N_init=None, hidden=Non
                    os.path.join(out_dir, f"model_{nq}dof"))
         np.save(os.path.join(out_dir, f"data_{nq}dof_al.npy"), np.asarray(X_iter))
     return dict(times=np.asarray(times), rmse=np.asarray(rmse), etpmax=np.asarray(etps), capped=capped,
-                march_s=march_s, device_march=use_device_march, queries=queries,
+                march_s=march_s, device_march=use_device_march, native_fit=use_native_fit, queries=queries,
                 scores=scores, labels=dict(counts), dropped=dropped, split=split, iterations=k,
                 cls_states=cls_states, guess_states=guess_states, batches=batches[1:], trainer=tr, guess_trainer=gt,
                 scorer=scorer, mean=mean, std=std, X_iter=X_iter, pool=Xu_iter, pool_rows=int(Xu_iter.shape[0]))
